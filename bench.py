@@ -1,6 +1,7 @@
 """Headline benchmark: env-steps/sec, 2-player Splendor, 65536 tables per MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--tables T] [--players P] [--mode rollout|step] [--only]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--tables T] [--players P] [--mode rollout|step]
+                    [--full [--only]] [--dump-outputs DIR]
     torchrun --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 `--gpus N` with N > 1 and no launcher in the environment (no WORLD_SIZE) starts its own N ranks
@@ -20,24 +21,37 @@ trajectories and write the same per-step outputs (tests/test_gpu_parity.py::test
                   Infinity Cache, so every output byte reaches HBM)
   --mode step     one spl_step launch per env step (the drop-in SplendorEnv.step path), timed as
                   captured HIP graphs of whole refill periods
-The mode not selected is measured too ("other_mode"), and the rollout kernel is measured a second
-time writing every step into the same [T, ...] block ("in_place_l3": that ~81 MB block stays
-resident in the Infinity Cache, so it is NOT an HBM figure and is never the headline).  Two more
-secondary lines: "config5_selfplay" (BASELINE config 5 per GPU: fused fp32 ActorCritic + batched
-dual step with the opponent pool, hipGraph replays) and "config4_share" (BASELINE config 4's
-per-GPU share: 4 players x 32768 tables, the same per-step rollout store, 8 launches timed).
+A plain run sets up, warms up, times the headline's --steps env steps and prints the JSON line.
 
---steps / --warmup are rounded UP to whole plan units (step_plan): a unit is two launches (the
-action buffers alternate) and whole pool-refill periods; "steps" in the JSON line is the number
-of env steps actually timed.  Warm-up is at least one unit (one full launch and one refill cycle).
+--full measures everything else too, as secondary lines of the same JSON line: the CPU baseline
+(at N = 1), the mode not selected ("other_mode"), the rollout kernel a second time writing every step
+into the same [T, ...] block ("in_place_l3": that ~81 MB block stays
+resident in the Infinity Cache, so it is NOT an HBM figure and is never the headline),
+"config5_selfplay" (BASELINE config 5 per GPU: fused fp32 ActorCritic + batched
+dual step with the opponent pool, hipGraph replays), "config4_share" (BASELINE config 4's
+per-GPU share: 4 players x 32768 tables, the same per-step rollout store, 8 launches timed) and
+"caller_path"; --only (with --full) keeps the CPU baseline and drops the other secondary lines.
+
+--steps is the number of env steps the headline times (headline_plan): in rollout mode whole
+128-step launches and, when --steps is no multiple of 128, one shorter last launch; "steps" and
+"ms_per_step" (wall time of the timed region / steps) in the JSON line say so.  --warmup is rounded
+UP to whole plan units: a unit is two launches and whole pool-refill periods, so warm-up is at least
+one full launch and one refill cycle.  The secondary measurements of --full round --steps up to whole
+units as well (step_plan: at least 8 launches, or 4 graph replays).
+
+--dump-outputs DIR writes, after the timed steps, what the headline's last timed step handed its
+caller (obs, mask, reward, terminated, flags, winner, final_obs of terminated tables, the next
+actions, the episode return sums and counts) as DIR/<name>.npy in float32: every table up to 16384,
+else a fixed seeded sample of 16384 tables (DIR/tables.npy; at N > 1, rank 0's tables).  Inputs are
+seeded, so two runs with the same arguments write the same files.
 
 Weak scaling: each rank owns `--tables` tables (global ids rank*T ...), no collective in the
 step path; after the timed region one all-gather (RCCL) collects episode returns.  value =
 tables x world x steps / max-over-ranks wall time.
 
 Printed on rank 0: ONE JSON line with the roofline of the headline kernel (HIP events around each
-launch inside the timed region, on the launch stream) and, at N=1, the CPU baseline (the C oracle
-port, one process per core, bounded sample).
+launch inside the timed region, on the launch stream) and, with --full at N=1, the CPU baseline (the
+C oracle port, one process per core, bounded sample).
 """
 import argparse
 import ctypes
@@ -90,6 +104,7 @@ PRECISION_DTYPE = {
 # the network's own fp32 work per table (2 x MACs of actor + critic), for the fp32-equivalent rate
 NET_FP32_FLOP = 2 * (297 * 256 + 256 * 256 + 256 * 45 + 297 * 256 + 256 * 256 + 256)
 ROLLOUT_K = 128    # env steps per spl_rollout launch = ppo_splendor.py's --num-steps default (:71)
+# the secondary measurements of --full (step_plan; the headline times --steps itself, headline_plan):
 MIN_TIMED_LAUNCHES = 8  # rollout mode times at least this many launches (>= 16 ms), whatever --steps says
 MIN_TIMED_REPLAYS = 4   # step mode (hipGraphs) times at least this many replays of a full graph (~12 ms)
 
@@ -136,6 +151,56 @@ def step_plan(mode, steps, warmup, refill_period, rollout_k=ROLLOUT_K, graph_ste
             m += unit
     return {"mode": mode, "per": per, "unit": unit, "K": k, "W": w, "G": g, "launches": k // per,
             "requested_steps": int(steps), "requested_warmup": int(warmup)}
+
+
+def headline_plan(mode, steps, warmup, refill_period, rollout_k=ROLLOUT_K, graph_steps=128):
+    """The headline's plan: --steps IS the number of env steps timed (step_plan, which rounds it up,
+    plans the secondary measurements of --full).
+
+    K      = steps timed = --steps (>= 1), exactly
+    W      = warm-up steps, as step_plan's (whole units, >= 1 unit)
+    sizes  = rollout mode: env steps of each timed launch, K // per launches of `per` steps and, when
+             K is no multiple of `per`, one last launch of the K % per steps left (spl_rollout takes
+             any step count; the action buffers alternate per launch whatever the count)
+    G      = step mode: steps per captured graph, the largest multiple of unit <= min(max(graph_steps,
+             unit), K), 0 (eager launches) when K < unit; `replays` = K // G replays are timed, then
+             the `tail` = K - replays * G steps left as eager launches inside the same timed region
+    """
+    base = step_plan(mode, steps, warmup, refill_period, rollout_k, graph_steps, min_launches=1, min_replays=1)
+    per, unit = base["per"], base["unit"]
+    k = max(int(steps), 1)
+    g = 0
+    if mode == "step" and graph_steps and graph_steps > 0:
+        g = min(max(int(graph_steps), unit), k) // unit * unit
+    sizes = [per] * (k // per) + ([k % per] if k % per else [])
+    return {"mode": mode, "per": per, "unit": unit, "K": k, "W": base["W"], "G": g, "launches": len(sizes),
+            "sizes": sizes, "replays": k // g if g else 0, "tail": k % g if g else k,
+            "requested_steps": int(steps), "requested_warmup": int(warmup)}
+
+
+DUMP_TABLES = 16384  # --dump-outputs: tables sampled from a larger batch (obs + final_obs rows: 39 MB as float32)
+
+
+def dump_sample(tables, limit=DUMP_TABLES):
+    """The table indices --dump-outputs writes: all of them up to `limit`, else a fixed seeded sample
+    (sorted, without replacement), the same on every run and every build."""
+    import numpy as np
+    if tables <= limit:
+        return np.arange(tables, dtype=np.int64)
+    return np.sort(np.random.default_rng(20240).choice(tables, size=limit, replace=False)).astype(np.int64)
+
+
+def dump_outputs(path, arrays, tables):
+    """Write each of `arrays` (name -> torch tensor whose first axis is the table) as path/<name>.npy in
+    float32, rows dump_sample(tables), and the sampled indices themselves as path/tables.npy (float64)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    idx = dump_sample(tables)
+    np.save(os.path.join(path, "tables.npy"), idx.astype(np.float64))
+    for name, t in arrays.items():
+        rows = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), rows.to(torch.float32).cpu().numpy())
 
 
 def _cpu_leg(players, procs, steps_per_proc):
@@ -631,7 +696,14 @@ def main():
                     help="rollout: one spl_rollout launch per "
                          f"{ROLLOUT_K} env steps; step: one spl_step launch per env step (same trajectories "
                          "and per-step outputs, tests/test_gpu_parity.py::test_rollout_equals_step_chain)")
-    ap.add_argument("--only", action="store_true", help="measure only --mode's headline variant")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the CPU baseline, the mode not selected, the "
+                         "in-place rollout, the config-5 and config-4 lines, the caller path (off: the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the headline's last timed step (and the next "
+                         f"actions, episode sums and counts) as DIR/<name>.npy, float32; batches above {DUMP_TABLES} "
+                         "tables are written as a fixed seeded sample of that many (DIR/tables.npy has the indices)")
+    ap.add_argument("--only", action="store_true", help="with --full: measure only --mode's headline variant")
     ap.add_argument("--outputs", choices=("store", "inplace"), default="store",
                     help="rollout mode: per-step blocks of a [K, T, ...] rollout store (headline) or every "
                          "step into the same block (L3-resident; labelled in_place_l3)")
@@ -671,7 +743,7 @@ def main():
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     rank_env = int(os.environ.get("RANK", "0"))
     cpu = None
-    if world_env == 1 and rank_env == 0 and not args.no_cpu_baseline:
+    if args.full and world_env == 1 and rank_env == 0 and not args.no_cpu_baseline:
         procs = args.cpu_procs or cpu_share()[0]
         cpu = cpu_baseline(args.players, procs, args.cpu_steps)
 
@@ -748,21 +820,26 @@ def main():
         bufs = get_store() if variant == "rollout_store" else eng_bufs
         return [mkargs(buf[0], buf[1], bufs), mkargs(buf[1], buf[0], bufs)]
 
+    issued = 0  # launches issued so far: each reads the action buffer the one before it wrote
+
     def run(variant, k0, k1, strm, ev=None, sargs=None):
         """Env steps k0..k1-1 (ply k+1 relative to ply_base).  variant "step": one spl_step launch
-        per step; "rollout_store"/"rollout_inplace": one spl_rollout launch per RK steps with
-        per-step blocks / in place.  Refills every R steps are issued by the library."""
+        per step; "rollout_store"/"rollout_inplace": one spl_rollout launch per RK steps (the last one
+        of fewer when k1 - k0 is no multiple of RK) with per-step blocks / in place.  Refills every R
+        steps are issued by the library."""
+        nonlocal issued
         per = 1 if variant == "step" else RK
         sargs = sargs or step_args(variant)
         for i, k in enumerate(range(k0, k1, per)):
-            sa = sargs[(k // per) & 1]
+            sa = sargs[issued & 1]
+            issued += 1
             sa.ply = k + 1
             if ev is not None:
                 ev[0][i].record()
             if variant == "step":
                 _native.check(lib, lib.spl_step(ctx, desc, ctypes.byref(sa), strm))
             else:
-                _native.check(lib, lib.spl_rollout(ctx, desc, ctypes.byref(sa), RK,
+                _native.check(lib, lib.spl_rollout(ctx, desc, ctypes.byref(sa), min(RK, k1 - k),
                                                    1 if variant == "rollout_store" else 0, strm))
             if ev is not None:
                 ev[1][i].record()
@@ -777,11 +854,13 @@ def main():
         return ([torch.cuda.Event(enable_timing=True) for _ in range(n)],
                 [torch.cuda.Event(enable_timing=True) for _ in range(n)])
 
-    def measure(variant, k_base):
+    def measure(variant, k_base, exact=False):
         """Warm up, time K steps; returns the timing record.  Steps are numbered from k_base so
-        every measurement continues the same trajectories with fresh policy counters."""
-        plan = step_plan("step" if variant == "step" else "rollout", args.steps, args.warmup, R, RK,
-                         args.graph_steps)
+        every measurement continues the same trajectories with fresh policy counters.  exact (the
+        headline): K is --steps itself (headline_plan); else step_plan's whole units."""
+        nonlocal issued
+        plan = (headline_plan if exact else step_plan)("step" if variant == "step" else "rollout", args.steps,
+                                                       args.warmup, R, RK, args.graph_steps)
         K, W, G, per = plan["K"], plan["W"], plan["G"], plan["per"]
         # warm-up: W steps, eager (also allocates the rollout store outside the timed region)
         ply_base.fill_(k_base)
@@ -789,6 +868,7 @@ def main():
         graph = None
         how = "eager launches, HIP events around each launch"
         if G > 0:
+            issued0 = issued
             try:
                 torch.cuda.synchronize(dev)
                 ply_base.fill_(k_base + W)
@@ -800,6 +880,7 @@ def main():
             except Exception as exc:  # capture unsupported: time eager launches instead
                 print(f"graph capture failed ({exc}); timing eager launches", file=sys.stderr)
                 graph, G = None, 0
+            issued = issued0  # captured, not run (and a replay is an even number of launches)
         warm_replays = 0
         if graph is not None:  # one untimed replay: the graph's first launch is not part of the measurement
             graph.replay()
@@ -807,21 +888,25 @@ def main():
         torch.cuda.synchronize(dev)
         eps0 = int(ep_cnt.sum().item())
         barrier(dev)
-        ev = events(K // G) if graph is not None else events(K // per)
+        replays = K // G if graph is not None else 0
+        tail = K - replays * G  # graphs: the steps no whole graph covers, eager, after the replays
+        ev = events(replays) if graph is not None else events(-(-K // per))
         sargs = step_args(variant)
         if graph is None:
             ply_base.fill_(k_base + W)
         for e in ev[0] + ev[1]:  # the HIP events are created on first record: outside the timed region
             e.record()
         torch.cuda.synchronize(dev)
-        region_mark(variant, "start", kernel_name(variant), K // per)
+        region_mark(variant, "start", kernel_name(variant), -(-K // per))
         t0 = time.perf_counter()
         if graph is not None:
             # recorded on the replay stream around each replay, not as graph nodes
-            for i in range(K // G):
+            for i in range(replays):
                 ev[0][i].record()
                 graph.replay()
                 ev[1][i].record()
+            if tail:
+                run(variant, 0, tail, stream, None, sargs)
         else:
             run(variant, 0, K, stream, ev, sargs)
         t_enq = time.perf_counter()
@@ -834,9 +919,20 @@ def main():
         print(f"[{variant}] timed region: wall {(t_sync - t0) * 1e3:.3f} ms (host enqueue "
               f"{(t_enq - t0) * 1e3:.3f} ms), GPU span first->last event {span * 1e3:.3f} ms", file=sys.stderr)
         terminations = int(ep_cnt.sum().item()) - eps0
+        if exact and args.dump_outputs and rank == 0:
+            # what the last timed step handed its caller, before anything else steps the tables: the last
+            # launch's last block of the rollout store, or the engine's own buffers
+            bufs = dict(eng_bufs)
+            if variant == "rollout_store":
+                bufs = {k: t[(K % per or per) - 1] for k, t in store.items()}
+            # final_obs rows are written for terminated tables only: the others are not outputs
+            bufs["final_obs"] = bufs["final_obs"] * (bufs["terminated"] != 0).to(torch.int32).unsqueeze(1)
+            bufs.update(next_actions=buf[issued & 1], ep_return=ep_ret, ep_count=ep_cnt)
+            dump_outputs(args.dump_outputs, bufs, T)
         kt = "HIP events around each launch in the timed region"
         k_next = k_base + W + warm_replays * G + K + 1
         eager_s = None
+        roof_per = per  # env steps of the launches the roofline is taken from
         if graph is not None:
             # ROCm rejects timing events as graph nodes ("External events are disallowed"), so the
             # per-launch time is each replay's event interval over its G launches (the graph's
@@ -845,43 +941,52 @@ def main():
             # the host dispatch latency of a ~20 us kernel).
             times = [ev[0][i].elapsed_time(ev[1][i]) / 1e3 / (G // per) for i in range(len(ev[0]))]
             launch_s = sum(times) / len(times)
-            kt = f"HIP events around each of {K // G} hipGraph replays ({G // per} launches each) in the timed region"
-            nwin = plan["unit"] * max(1, -(-64 // plan["unit"]))
-            ev = events(nwin // per)
-            ply_base.fill_(k_next)
-            run(variant, 0, nwin, stream, ev)
-            torch.cuda.synchronize(dev)
-            eager_s = sum(ev[0][i].elapsed_time(ev[1][i]) for i in range(len(ev[0]))) / len(ev[0]) / 1e3
-            k_next += nwin + 1
+            kt = f"HIP events around each of {replays} hipGraph replays ({G // per} launches each) in the timed region"
+            if tail:
+                how += f", then {tail} eager launches"
+            if args.full:  # a run of its own
+                nwin = plan["unit"] * max(1, -(-64 // plan["unit"]))
+                ev = events(nwin // per)
+                ply_base.fill_(k_next)
+                run(variant, 0, nwin, stream, ev)
+                torch.cuda.synchronize(dev)
+                eager_s = sum(ev[0][i].elapsed_time(ev[1][i]) for i in range(len(ev[0]))) / len(ev[0]) / 1e3
+                k_next += nwin + 1
         else:
             times = [ev[0][i].elapsed_time(ev[1][i]) / 1e3 for i in range(len(ev[0]))]
+            if K % per and K > per:  # the roofline is the full launches': the shorter last one left out
+                times = times[:-1]
+            elif K < per:
+                roof_per = K
             launch_s = sum(times) / len(times)
         return {"variant": variant, "plan": plan, "elapsed": elapsed, "launch_s": launch_s, "times": times, "how": how,
-                "kernel_timing": kt, "terminations": terminations, "k_next": k_next, "eager_s": eager_s}
+                "kernel_timing": kt, "terminations": terminations, "k_next": k_next, "eager_s": eager_s,
+                "roof_per": roof_per}
 
     headline = "step" if args.mode == "step" else ("rollout_store" if args.outputs == "store" else "rollout_inplace")
     variants = [headline]
-    if not args.only:
+    beside = args.full and not args.only  # everything beside the headline is --full's
+    if beside:
         variants += [v for v in ("rollout_store", "rollout_inplace", "step") if v != headline]
     recs, k_next = {}, 0
     handoffs = None
     for v in variants:
         if v == "rollout_store":
             partner_stats(lib, clear=True)
-        recs[v] = measure(v, k_next)
+        recs[v] = measure(v, k_next, exact=v == headline)
         k_next = recs[v]["k_next"]
         if v == "rollout_store" and headline == "rollout_store":  # this line's hand-offs (warm-up included)
             handoffs = partner_stats(lib)
     sp = sp2 = None
-    if args.sp_tables > 0 and not args.only:
+    if args.sp_tables > 0 and beside:
         sp = selfplay_line(dev, rank, world, args.sp_tables, args.sp_iters, warmup=8, precision="fp32")
         sp2 = selfplay_line(dev, rank, world, args.sp_tables, args.sp_iters, warmup=8, precision="fp32_f16x2")
     c4 = None
-    if args.c4_tables > 0 and not args.only and args.players == 2:
+    if args.c4_tables > 0 and beside and args.players == 2:
         c4 = c4_share_line(dev, rank, world, args.c4_tables, launches=8, warmup=2, pipeline=args.c4_pipeline,
                            partner_lead=args.partner_lead)
     caller = None
-    if args.caller_envs > 0 and not args.only and rank == 0 and args.players == 2:
+    if args.caller_envs > 0 and beside and rank == 0 and args.players == 2:
         caller = caller_path_line(args.caller_envs)
     # correctness canaries on the measured run: no error flags, episodes completed
     errs = _native.F_OOB | _native.F_AFTER_TERMINAL | _native.F_RNG_LIMIT | _native.F_FAULT
@@ -894,15 +999,14 @@ def main():
 
     def summary(rec):
         v, plan = rec["variant"], rec["plan"]
-        K, per = plan["K"], plan["per"]
-        launches = K // per
+        K, per = plan["K"], rec["roof_per"]
         if v == "step":
             algo = STEP_ALGO_BYTES[P] * T
             algo_note = (f"{STEP_ALGO_BYTES[P]} B per table-step (SURVEY.md §8d: 2*S_P + obs + mask + action + reward + "
                          f"terminated = {STEP_ALGO_BYTES[P] - LEGAL_CACHE_BYTES}, + {LEGAL_CACHE_BYTES} B of legal-mask cache)")
         else:
             # state read+write once per launch, first/next actions, per-step outputs, terminal rows
-            term_per_launch = rec["terminations"] / launches
+            term_per_launch = rec["terminations"] * per / K
             algo = (2 * STATE_BYTES[P] + 8) * T + OUT_BYTES * T * per + OBS_ROW * term_per_launch
             algo_note = (f"2*S_P/{per} + {OUT_BYTES} B per table-step (obs 1188 + mask 45 + reward 4 + terminated/flags/"
                          f"winner 3) + 8 B/table of actions per launch + 1188 B per terminal row "
@@ -920,7 +1024,7 @@ def main():
                      "frac": round(achieved / HBM_PEAK_GBS, 4),
                      "frac_of_achievable": round(achieved / HBM_ACHIEVABLE_GBS, 4)}
         return {"variant": v, "value": round(T * world * K / rec["elapsed"], 1),
-                "steps": K, "ms_per_step": round(rec["elapsed"] / K * 1e3, 4),
+                "steps": K, "ms_per_step": round(rec["elapsed"] / K * 1e3, 7),
                 "roofline": {**bound,
                              "kernel": kernel_name(v), "steps_per_launch": per,
                              "kernel_avg_us": round(rec["launch_s"] * 1e6, 2),
@@ -934,7 +1038,7 @@ def main():
 
     def with_traffic(s):
         """The variant's summary with the committed PMC HBM bytes per launch of its kernel."""
-        traffic, traffic_src = load_pmc_traffic(s["roofline"]["kernel"], T, s["plan"]["per"])
+        traffic, traffic_src = load_pmc_traffic(s["roofline"]["kernel"], T, s["roofline"]["steps_per_launch"])
         s["roofline"].update(traffic=traffic, traffic_source=traffic_src,
                              traffic_over_algo=None if traffic is None
                              else round(traffic / s["roofline"]["algo_bytes_per_launch"], 4))
@@ -967,7 +1071,8 @@ def main():
                        "delegation": args.delegation,
                        "launch": main_s["launch"], "requested_steps": plan["requested_steps"],
                        "requested_warmup": plan["requested_warmup"],
-                       "step_rounding": f"steps/warmup rounded up to whole units of {plan['unit']} (step_plan)"},
+                       "step_rounding": f"steps timed = --steps; warm-up rounded up to whole units of {plan['unit']} "
+                                        "(headline_plan)"},
             "roofline": roof,
             "cpu_baseline": cpu,
             "episodes": episodes,

@@ -26,29 +26,29 @@ for step in "$@"; do
     faults) run pytest_faults 400 python -u -m pytest tests/test_gpu_faults.py tests/test_gpu_env_api.py \
                 tests/test_gpu_parity.py -k "fault or dealer or edited or rollout_equals" -x -v --timeout 200 --timeout-method thread ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    driver) run bench_driver 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 ;;
+    driver) run bench_driver 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full ;;
     prof)
       # the driver's exact command under rocprofv3: one summary row per kernel instantiation
       run prof_driver 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_driver_$TAG -o run -- \
-          python3 bench.py --gpus 1 --steps 20 --warmup 5
+          python3 bench.py --gpus 1 --steps 20 --warmup 5 --full
       cp $O/prof_driver_$TAG/run_kernel_stats.csv $O/kernel_stats_driver_$TAG.csv 2>/dev/null || \
           find $O/prof_driver_$TAG -name '*kernel_stats.csv' -exec cp {} $O/kernel_stats_driver_$TAG.csv \;
       head -8 $O/kernel_stats_driver_$TAG.csv
       # the same trace averaged over the timed launches only (bench.py's region marks)
       python3 tools/trace_timed.py $(find $O/prof_driver_$TAG -name '*kernel_trace.csv' | head -1) \
-          $O/prof_driver_${TAG}.err --source "rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps 20 --warmup 5 ($TAG)" \
+          $O/prof_driver_${TAG}.err --source "rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full ($TAG)" \
           --out $O/kernel_trace_timed_$TAG.json | head -60 ;;
     deleg) run deleg_ab 600 python3 tools/deleg_ab.py --rounds 12 --arms 0,6 ;;
     profc4)
       run prof_c4 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c4_$TAG -o run -- \
-          python3 bench.py --no-cpu-baseline --players 4 --tables 32768
+          python3 bench.py --full --no-cpu-baseline --players 4 --tables 32768
       cp $O/prof_c4_$TAG/run_kernel_stats.csv $O/kernel_stats_c4_$TAG.csv; head -5 $O/kernel_stats_c4_$TAG.csv | cut -c1-160 ;;
     pmcc4) bash tools/pmc.sh ${TAG}_4p_32768 4 32768 store all || exit 1
            bash tools/pmc.sh ${TAG}_4p_32768_inplace 4 32768 inplace traffic || exit 1 ;;
     multi)
-      run bench_3p 600 python3 bench.py --no-cpu-baseline --players 3
-      run bench_4p 600 python3 bench.py --no-cpu-baseline --players 4
-      run bench_4p_32768 600 python3 bench.py --no-cpu-baseline --players 4 --tables 32768 ;;
+      run bench_3p 600 python3 bench.py --full --no-cpu-baseline --players 3
+      run bench_4p 600 python3 bench.py --full --no-cpu-baseline --players 4
+      run bench_4p_32768 600 python3 bench.py --full --no-cpu-baseline --players 4 --tables 32768 ;;
     pmc2p) bash tools/pmc.sh ${TAG}_2p 2 65536 store all || exit 1
            bash tools/pmc.sh ${TAG}_2p_inplace 2 65536 inplace traffic || exit 1
            bash tools/pmc.sh ${TAG}_2p_step 2 65536 step all || exit 1 ;;
@@ -128,7 +128,7 @@ for step in "$@"; do
     poltest1) run pytest_pol1 300 python -u -m pytest tests/test_gpu_policy.py -x -q --timeout 200 --timeout-method thread ;;
     selfplay) run sp_pool 300 python tools/bench_selfplay.py
               run sp_frozen 300 python tools/bench_selfplay.py --opponent frozen ;;
-    bench) run bench_default 600 python3 bench.py ;;
+    bench) run bench_default 600 python3 bench.py --full ;;
     stepmode) run bench_step 300 python3 bench.py --mode step --only --no-cpu-baseline --sp-tables 0
               run prof_step 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_step_$TAG -o run -- \
                   python3 bench.py --mode step --only --no-cpu-baseline --sp-tables 0
@@ -136,7 +136,7 @@ for step in "$@"; do
     rank2)  # the driver's N>1 launch rehearsed with 2 ranks on this one card (collectives over gloo)
       export SPLENDOR_DIST_BACKEND=gloo
       run bench_2rank 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-          --master-addr 127.0.0.1 --master-port 29531 bench.py --gpus 2 --steps 20 --warmup 5
+          --master-addr 127.0.0.1 --master-port 29531 bench.py --gpus 2 --steps 20 --warmup 5 --full
       unset SPLENDOR_DIST_BACKEND ;;
     vec) run vec_step 300 python tools/bench_vec_step.py
          run prof_vec 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_vec_$TAG -o run -- python3 tools/bench_vec_step.py

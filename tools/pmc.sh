@@ -17,7 +17,7 @@ COMMON="--no-cpu-baseline --only --players $P --tables $T"
 if [ "$VARIANT" = "step" ]; then
   ARGS="$COMMON --mode step --graph-steps 0 --steps 64 --warmup 64"
 else
-  ARGS="$COMMON --mode rollout --outputs $VARIANT --steps 128 --warmup 128"
+  ARGS="$COMMON --mode rollout --outputs $VARIANT --steps 1024 --warmup 128"
 fi
 TRAFFIC="FETCH_SIZE;WRITE_SIZE"
 MORE="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU;\

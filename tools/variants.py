@@ -47,7 +47,7 @@ def build(specs):
 def bench(names, extra):
     for name in names:
         env = dict(os.environ, SPLENDOR_AMD_LIB=os.path.join(OUTD, f"lib_{name}.so"))
-        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--no-cpu-baseline", *extra], env=env,
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--no-cpu-baseline", *extra], env=env,
                            capture_output=True, text=True, timeout=600)
         if r.returncode != 0:
             print(name, "FAILED", r.stderr[-2000:])
