@@ -166,7 +166,7 @@ int spl_ctx_set_rollout_pipeline(spl_ctx_t *ctx, int on);
  * neighbouring even XCC, which encodes the rows and stores them into the rollout store after its
  * own steps: MI355X's odd XCCs drain stores ~20 % slower, and the slowest sets the launch time.
  * Turned off for grids larger than the resident workgroup capacity (pairs might not run together).
- * Default: SPL_DELEG_EVERY (DESIGN.md §2 gives the measured A/B).  Results are identical either way. */
+ * Default: 0, off (DESIGN.md §2 gives the measured A/B).  Results are identical either way. */
 int spl_ctx_set_rollout_delegation(spl_ctx_t *ctx, int every);
 /* Partner hand-off of the rollout store in the kernels that run one workgroup per CU with the grid
  * resident at once: the six-wave dealer (k_rollout_store_dealer2_<P>p, 384 threads) and the quad

@@ -84,9 +84,10 @@ constexpr int kObsU8 = 300;  // compact observation row (spl_step_args_t.obs_u8)
 #ifndef SPL_ABL
 #define SPL_ABL 0
 #endif
-constexpr int ABL_LEGAL_PRE = 1, ABL_APPLY = 2, ABL_LEGAL_POST = 4, ABL_FINAL = 8, ABL_RESET = 16, ABL_ENCODE = 32,
-              ABL_STORE = 64, ABL_MASK_STORE = 128, ABL_SMALL_OUT = 256, ABL_TAB_STORE = 512, ABL_OBS_STORE = 1024,
-              ABL_LOAD = 2048, ABL_TOKLIM = 4096, ABL_NOBLE = 8192, ABL_DECK_GATHER = 16384, ABL_LUT_GATHER = 32768;
+// (bits 16, 64, 512 and 2048 belonged to the one-wave step kernel; the others keep the values past profiles quote)
+constexpr int ABL_LEGAL_PRE = 1, ABL_APPLY = 2, ABL_LEGAL_POST = 4, ABL_FINAL = 8, ABL_ENCODE = 32,
+              ABL_MASK_STORE = 128, ABL_SMALL_OUT = 256, ABL_OBS_STORE = 1024,
+              ABL_TOKLIM = 4096, ABL_NOBLE = 8192, ABL_DECK_GATHER = 16384, ABL_LUT_GATHER = 32768;
 __device__ __forceinline__ bool abl(int bit) { return (SPL_ABL & bit) != 0; }
 
 // Bounds-check build (-DSPL_BOUNDS_CHECK; libsplendor_amd_checked.so, tests/test_gpu_bounds_check.py):
@@ -111,7 +112,7 @@ enum : uint32_t {
 };
 
 // Phase stamps for the diagnostic build only (-DSPL_STAMPS, tools/stamps.py): lane 0 of every
-// wave records s_memrealtime (100 MHz) at phase boundaries of k_step.  Never in the product build.
+// wave records s_memrealtime (100 MHz) at phase boundaries of step_ws.  Never in the product build.
 #ifdef SPL_STAMPS
 __device__ uint64_t *g_stamps;
 #define STAMP(i)                                                                                 \
@@ -176,88 +177,45 @@ __device__ int g_stream_limit = MTStream::kMaxOut;
 
 // Per-lane deal scratch in LDS: an odd number of dwords, so lanes at the same Fisher-Yates
 // position (the common case: lanes decrement their index in step) hit 64 different banks.
-#ifndef SPL_SCRATCH_STRIDE
-#define SPL_SCRATCH_STRIDE 116
-#endif
-constexpr int kScratchStride = SPL_SCRATCH_STRIDE;
-#ifndef SPL_DELEG_EVERY
-// rollout-store delegation period (spl_ctx_set_rollout_delegation): off by default.  Alternating
+constexpr int kScratchStride = 116;
+// rollout-store delegation period a context starts with (spl_ctx_set_rollout_delegation): off.  Alternating
 // A/B on one box, 12 launches per arm of 128 steps at 65 536 tables: 1999 +- 25 us off vs
 // 1969 +- 34 us every 6th step, a 1.5 % gain (profiles/r03/deleg_ab_r03a.txt) -- under the 2 %
 // that would pay for a cross-XCC hand-off in the headline kernel
-#define SPL_DELEG_EVERY 0
-#endif
-#ifndef SPL_PARTNER_LEAD
+constexpr int kDelegEveryDefault = 0;
 // partner hand-off of the one-workgroup-per-CU rollout stores (six-wave dealer, quad; spl_ctx_set_partner_lead):
 // a team hands a step's rows to its neighbouring-XCC partner when that one is this many steps ahead.
-// Default 0 (off) since round 6's sc0 nt sc1 row stores (SPL_ROLL_CPOL): the teams then lag far less and
-// the polls cost more than the hand-off recovers — quad lead 0 / 4 / 8: 1 873-1 898 / 1 909-1 925 /
+// A context starts with 0 (off) since round 6's sc0 nt sc1 row stores (kRollCpol): the teams then lag far less
+// and the polls cost more than the hand-off recovers — quad lead 0 / 4 / 8: 1 873-1 898 / 1 909-1 925 /
 // 1 912-1 913 us per launch (another box: lead 0 / 4 1 863-1 873 / 1 892-1 900,
 // profiles/r06/quad_lead_ab_r06ad.txt); six-wave dealer (C4) 1 075-1 078 / 1 081-1 100 / 1 083-1 102
 // (profiles/r06/c4_lead_ab_r06ag.txt).  With nt-only stores lead 4 had paid 2.4 % (headline,
 // profiles/r06/headab_r06d.txt) and ~2 % (C4, profiles/r04/partner_ab_r04u.txt).
-#define SPL_PARTNER_LEAD 0
-#endif
-#ifndef SPL_XCD_MAP
-#define SPL_XCD_MAP 1
-#endif
+constexpr int kPartnerLeadDefault = 0;
 // Workgroup -> 64-table block, XCD-contiguous.  The dispatcher hands workgroup b to XCD b % 8, so
 // with the identity map every XCD writes every eighth 76 KB chunk of a step's rollout-store block;
 // mapped, XCD x's workgroups own tables [x n/8, (x+1) n/8) and each XCD streams one contiguous eighth
 // of the block (store-only pattern: 880 -> 844-862 us per 64 steps on one box,
 // tools/microbench_hbm_store.hip rows_x).  Only which workgroup steps which tables changes: every
-// table's chain is its own, so results are identical (A/B build switch SPL_XCD_MAP=0).
+// table's chain is its own, so results are identical.  A grid that is no multiple of 8 keeps the identity.
 __device__ __forceinline__ int wg_block_of(uint32_t b) {
     const uint32_t nb = gridDim.x;
-    if (!SPL_XCD_MAP || (nb & 7u)) return (int)b;
+    if (nb & 7u) return (int)b;
     return (int)((b & 7u) * (nb >> 3) + (b >> 3));
 }
 __device__ __forceinline__ int wg_block() { return wg_block_of(blockIdx.x); }
-#ifndef SPL_STEP_OBS_NT
-#define SPL_STEP_OBS_NT false  // k_step_ws observation stores non-temporal (A/B switch)
-#endif
-// k_step_wst (at most three workgroups per CU) stores its int32 rows through the NT output stream
-// (SPL_ROLL_CPOL's sc0 nt sc1): per step 17.1 -> 16.0 us at 32 768 tables, 14.8 -> 12.8 at 16 384,
-// 12.7 -> 12.2 at 4 096 (profiles/r06/step_tail_store_ab_r06y.txt), where at 65 536 tables (k_step_ws)
-// non-temporal rows cost 22.4 -> 23.8 us (profiles/r06/step_store_policy_ab_r06x.txt)
-#ifndef SPL_STEP_TAIL_NT
-#define SPL_STEP_TAIL_NT true
-#endif
-// k_step_ws (four workgroups per CU) stores its int32 rows as `sc1` buffer stores (system scope, temporal;
-// -2 = plain): 22.35 -> 20.5 us per step at 65 536 tables; `sc0 sc1` the same, `sc0` alone as plain
-// (profiles/r06/step_ws_temporal_policy_r06an.txt); non-temporal rows were slower there (23.8 us)
-// the three-wave step's row policy (-3: SPL_STEP_TAIL_NT's stream): `sc1` (16), per step 15.98 -> 15.07 us at
-// 32 768 tables, 20.0 -> 18.2 at 49 152, 12.85 -> 12.82 at 16 384 against sc0 nt sc1
-// (profiles/r06/step_tail_sc1_ab_r06ap.txt)
-#ifndef SPL_STEP_TAIL_CPOL
-#define SPL_STEP_TAIL_CPOL 16
-#endif
-// A/B switch: spl_step's mask block store policy (-2 plain)
-#ifndef SPL_STEP_MASK_CPOL
-#define SPL_STEP_MASK_CPOL -2
-#endif
-#ifndef SPL_STEP_WS_CPOL
-#define SPL_STEP_WS_CPOL 16
-#endif
-// A/B switch: k_step_ws stores the first (1) or second (2) half of its row block through the NT output
-// stream and the other half plain (0: all plain)
-#ifndef SPL_STEP_WS_SPLIT
-#define SPL_STEP_WS_SPLIT 0
-#endif
-#ifndef SPL_STEP_BOTH_NT
-#define SPL_STEP_BOTH_NT 0
-#endif
-struct NoOp {
-    __device__ __forceinline__ void operator()() const {}
-};
-#ifndef SPL_WS_PRIO
-#define SPL_WS_PRIO 1
-#endif
-// per-step rollout-store rows and masks non-temporal (1, round 2's choice) or plain (0): A/B switch
-#ifndef SPL_ROLL_NT
-#define SPL_ROLL_NT 1
-#endif
-constexpr bool kRollNT = SPL_ROLL_NT != 0;
+// spl_step's int32 rows leave k_step_ws and k_step_wst as `sc1` buffer stores (16: system scope, temporal).
+// k_step_ws (four workgroups per CU): 22.35 -> 20.5 us per step at 65 536 tables against plain stores,
+// `sc0 sc1` the same, `sc0` alone as plain (profiles/r06/step_ws_temporal_policy_r06an.txt); non-temporal
+// rows cost 22.4 -> 23.8 us there (profiles/r06/step_store_policy_ab_r06x.txt), half the block non-temporal
+// 22.2 vs 22.4 (profiles/r06/step_ws_split_policy_r06z.txt), non-temporal rows beside a compact copy neutral
+// (profiles/r06/dual_opp_rows_nt_r06aa.txt).
+// k_step_wst (at most three workgroups per CU): 15.98 -> 15.07 us at 32 768 tables, 20.0 -> 18.2 at 49 152,
+// 12.85 -> 12.82 at 16 384 against sc0 nt sc1 (profiles/r06/step_tail_sc1_ab_r06ap.txt), which itself had
+// beaten plain stores 17.1 -> 16.0 us at 32 768 tables (profiles/r06/step_tail_store_ab_r06y.txt).
+// k_step_wso keeps plain stores (store_obs_block_mid), and so does every spl_step mask block (sc1 there:
+// 20.79 vs 20.62 us at 65 536 tables, equal at 32 768; profiles/r06/step_mask_policy_ab_r06ar.txt).
+constexpr int kStepRowCpol = 16;
 
 constexpr int kMaskStreamWords = 64 * 45 / 32;  // 90
 
@@ -272,14 +230,9 @@ struct __align__(16) WaveBuf {
     uint64_t mask[64];
     uint32_t mbits[96];  // the wave's 64 x 45 mask bits as one stream (store_mask_block)
     uint8_t rows[64 * kObsDim];   // observation staging; also the deal scratch (64 x 112 B)
-    uint8_t frows[64 * kObsDim];  // terminal observations (k_step): stored with everything else at the end
+    uint8_t frows[64 * kObsDim];  // terminal observations (k_rollout): stored with the step's other outputs
 };
 struct __align__(16) BlockLDS : Consts, WaveBuf {};
-// k_step with W waves (64 tables each) per workgroup: one copy of the constant tables
-template <int W>
-struct __align__(16) StepLDS : Consts {
-    WaveBuf w[W];
-};
 
 // ------------------------------------------------------------------------------------------
 // small helpers
@@ -1061,33 +1014,22 @@ __device__ __forceinline__ void store_row_direct(const Tab<P> &T, const Consts &
 // unrolled copy, splits every store into four strided dword stores (half the store bandwidth).
 typedef int v4i __attribute__((ext_vector_type(4)));
 
-// Output-stream store of one 16-byte vector.  NT (the per-step rollout store, written once and
-// not read back by this launch): non-temporal, so the 5 GB stream does not push the token table,
-// deck records and state out of L2 / the Infinity Cache — the rules wave's gathers stay fast
-// (rollout store 1225 -> 1109 us per 64 steps at 65 536 tables).  In-place outputs keep plain
-// stores: their block stays Infinity-Cache resident for the consumer (NT: 794 -> 1020 us).
-template <bool NT>
-__device__ __forceinline__ void st_v4(v4i *p, v4i v) {
-    if (NT) __builtin_nontemporal_store(v, p);
-    else *p = v;
-}
-
-// Cache policy of the NT output stream (the rollout store's per-step rows and masks): >= 0 a buffer store
-// with that cache-policy immediate (gfx950: sc0 = 1, nt = 2, sc1 = 16) on a resource over the block; -1 the
-// compiler's non-temporal store (`global_store_dwordx4 … nt`).  Default 19 = `sc0 nt sc1` (system scope,
-// non-temporal): headline 1 941-1 952 against 1 975-2 002 us per launch with `nt` alone, four alternations
-// on one box, 1.4 % on another; without nt 12 % slower (profiles/r06/store_policy_ab_r06u_v.txt)
-#ifndef SPL_ROLL_CPOL
-#define SPL_ROLL_CPOL 19
-#endif
-// A/B switch: the rollout store's terminal rows and small outputs (reward, terminated, flags, winner)
-// through the same policy (0: plain stores)
-#ifndef SPL_ROLL_SMALL_NT
-#define SPL_ROLL_SMALL_NT 0
-#endif
+// The two output streams of a rollout.  NT: the per-step rollout store's row and mask blocks (written once
+// and not read back by this launch) leave non-temporal, so the 5 GB stream does not push the token table,
+// deck records and state out of L2 / the Infinity Cache — the rules wave's gathers stay fast (rollout store
+// 1225 -> 1109 us per 64 steps at 65 536 tables; plain 13-22 % slower in the kernel, profiles/r06/roll_nt_ab_r06m.txt).
+// In-place outputs keep plain stores: their block stays Infinity-Cache resident for the consumer (NT: 794 ->
+// 1020 us).  So do the store's terminal rows and small outputs (through the NT stream: headline 1 972-1 984 vs
+// 1 936-1 955 us, C4 1 177-1 178 vs 1 065-1 067; profiles/r06/small_outputs_nt_ab_r06ai.txt).
+// The NT stream is a buffer store with a cache-policy immediate (gfx950: sc0 = 1, nt = 2, sc1 = 16) on a
+// resource over the block: 19 = `sc0 nt sc1` (system scope, non-temporal), headline 1 941-1 952 against
+// 1 975-2 002 us per launch with `nt` alone, four alternations on one box, 1.4 % on another; without nt
+// 12 % slower (profiles/r06/store_policy_ab_r06u_v.txt)
+constexpr int kRollCpol = 19;
+constexpr int kPlainCpol = -2;
 typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
-// 16-byte output stores into one wave-uniform block under cache policy CP: -2 plain, -1 the compiler's
-// non-temporal store, >= 0 a buffer store with that cache-policy immediate
+// 16-byte output stores into one wave-uniform block under cache policy CP: kPlainCpol plain stores, >= 0 a
+// buffer store with that cache-policy immediate
 template <int CP>
 struct V4Sink {
     v4i *out;
@@ -1097,11 +1039,11 @@ struct V4Sink {
     }
     __device__ __forceinline__ void put(int i, v4i v) const {
         if constexpr (CP >= 0) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, v), rs, i * 16, 0, CP);
-        else st_v4<CP == -1>(out + i, v);
+        else out[i] = v;
     }
 };
-// the policy of an output stream: the NT stream (SPL_ROLL_CPOL) or plain stores
-constexpr int stream_cpol(bool nt) { return nt ? SPL_ROLL_CPOL : -2; }
+// the policy of an output stream: the NT stream or plain stores
+constexpr int stream_cpol(bool nt) { return nt ? kRollCpol : kPlainCpol; }
 
 __device__ __forceinline__ v4i expand4(uint32_t w) {
     v4i v = {(int)(w & 0xFFu), (int)((w >> 8) & 0xFFu), (int)((w >> 16) & 0xFFu), (int)(w >> 24)};
@@ -1167,17 +1109,16 @@ __device__ __forceinline__ void store_obs_block(const uint8_t *rows_lds, int row
 }
 
 // store_obs_block (64 rows) with `mid()` issued between its first and second half: work that fills the
-// wave's store-issue stalls instead of following the whole block (k_step_wso's legal mask)
-template <bool NT, class Mid, bool NT2 = NT>
+// wave's store-issue stalls instead of following the whole block (k_step_wso's legal mask).  Plain stores.
+template <class Mid>
 __device__ __forceinline__ void store_obs_block_mid(const uint8_t *rows_lds, int rows, int32_t *dst, Mid mid) {
     if (rows != 64) {
         mid();
-        store_obs_block<64, NT>(rows_lds, rows, dst);
+        store_obs_block<64, false>(rows_lds, rows, dst);
         return;
     }
     const uint32_t *src = reinterpret_cast<const uint32_t *>(rows_lds);
-    const V4Sink<stream_cpol(NT)> out(dst);
-    const V4Sink<stream_cpol(NT2)> out2(dst);  // the second half (and the tail) may take another store policy
+    const V4Sink<kPlainCpol> out(dst);
     constexpr int U = 5, kFull = 64 * kObsDim / 4, kIters = kFull / (64 * U);  // 4752 = 14 x 320 + 272
     int d = lane_id();
 #pragma unroll 1
@@ -1197,14 +1138,14 @@ __device__ __forceinline__ void store_obs_block_mid(const uint8_t *rows_lds, int
 #pragma unroll
         for (int u = 0; u < U; ++u) w[u] = src[d + 64 * u];
 #pragma unroll
-        for (int u = 0; u < U; ++u) out2.put(d + 64 * u, expand4(w[u]));
+        for (int u = 0; u < U; ++u) out.put(d + 64 * u, expand4(w[u]));
     }
     uint32_t w[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) w[u] = (d + 64 * u < kFull) ? src[d + 64 * u] : 0u;
 #pragma unroll
     for (int u = 0; u < U; ++u)
-        if (d + 64 * u < kFull) out2.put(d + 64 * u, expand4(w[u]));
+        if (d + 64 * u < kFull) out.put(d + 64 * u, expand4(w[u]));
 }
 
 // Block store of `rows` compact rows (300 bytes each) staged in LDS to dst (16-byte aligned).
@@ -1645,7 +1586,7 @@ __global__ __launch_bounds__(64) void k_build_lut(uint4 *lut) {
     lut[e] = make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-// ---- one env step of one table, shared by k_step and k_rollout ----------------------------
+// ---- one env step of one table, shared by step_ws and the rollouts ----------------------------
 
 // Loads a step needs beyond the table state, issued as early as the action is known: the deck
 // card the action pops and the token-return table entry it consults (predict_lut_key).
@@ -1933,23 +1874,6 @@ __device__ __forceinline__ void store_row_columns(const uint32_t *st, int stride
         if (e < kObsDim) dst[e] = (int32_t)v[i];
     }
 }
-// the same through the NT output stream's cache policy (SPL_ROLL_CPOL; dst wave-uniform)
-template <int P>
-__device__ __forceinline__ void store_row_columns_nt(const uint32_t *st, int stride, const Consts &L, const ColRecipes &C,
-                                                     int32_t *dst) {
-#if SPL_ROLL_CPOL >= 0
-    uint32_t v[5];
-    row_columns<P>(st, stride, L, C, v);
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(dst, (short)0, kObsDim * 4, 0x00020000);
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-        const int e = lane_id() + 64 * i;
-        if (e < kObsDim) __builtin_amdgcn_raw_buffer_store_b32(v[i], rs, e * 4, 0, SPL_ROLL_CPOL);
-    }
-#else
-    store_row_columns<P>(st, stride, L, C, dst);
-#endif
-}
 // spl_step_args_t.gate_*: the dual step's opponent moves only where the agent's move was applied
 // and left the game running (wrappers/dual_step_native.py:120-140, spl_dual_gate); elsewhere its
 // action becomes -1 (out of range: no move), written back so the caller sees the gated action.
@@ -1979,120 +1903,8 @@ __device__ __forceinline__ void store_step_info(const KStep &S, int n, int t, bo
     }
 }
 
-// SplendorEnv.step for every table (envs/splendor_env.py:51-90) + same-step autoreset.
-//
-// Every global load of the step (state, action, pool deal words, the deck card the action
-// pops, the token-return table entry it consults) is issued in the first microseconds, before
-// any wave has started its stores; from there to the block stores at the end the wave touches
-// only registers and LDS.  A load issued later would queue behind the other waves' observation
-// writes (tens of MB in flight) and its wave would become the kernel's tail.
-//
-// W waves per workgroup (64 tables each, independent except for the shared constant tables):
-// fewer, larger workgroups reach the whole chip sooner than 64-thread ones.
-template <int P, int W>
-__global__ __launch_bounds__(64 * W) void k_step(KArena A, KTables Tb, KStep S) {
-    __shared__ StepLDS<W> SL;
-    Consts &L = SL;
-    const int wave = W == 1 ? 0 : (int)(threadIdx.x >> 6);
-    WaveBuf &B = SL.w[wave];
-    const int lane = lane_id();
-    const int t0 = (blockIdx.x * W + wave) * 64;
-    const int t = t0 + lane;
-    const bool valid = t < A.n;
-    const int rows = max(0, min(64, A.n - t0));
-    STAMP(0);
-    if (W == 1) {
-        load_tables_lds(L, Tb);
-    } else {
-        for (int i = threadIdx.x; i < 90; i += 64 * W) L.cards[i] = Tb.cards[i];
-        if (threadIdx.x < 10) L.nobles[threadIdx.x] = Tb.nobles[threadIdx.x];
-    }
-
-    Tab<P> T;
-    int action = 0;
-    Deal pool = empty_deal();
-    if (valid && !abl(ABL_LOAD)) {
-        load_tab(T, A, t);
-        action = gated_action(S, t);
-        if (S.autoreset) pool = load_pool(A, t);
-    } else {
-        fresh_state(T, 0u, empty_deal());
-    }
-    if (W == 1) wave_lds_sync();
-    else __syncthreads();  // the constant tables (nothing stored yet: no store drain to wait for)
-    const StepPre pre = step_prefetch(T, action, valid, A, t, Tb);
-    STAMP(1);
-
-    // LDS for a token-return continuation (LaneMT): the observation rows past the deal scratch
-    uint32_t *const mtx = reinterpret_cast<uint32_t *>(&B.rows[64 * kScratchStride]);
-    StepOut o = step_rules(T, action, pre, valid, L, Tb, mtx);
-    // autoreset 2: a table terminal on entry is re-dealt without a move (dual-step opponent phase)
-    const bool entry_reset = valid && S.autoreset == 2 && (o.flags & SPL_F_AFTER_TERMINAL);
-    if (entry_reset) o.flags = 0u;
-    const bool ended = valid && (o.term || entry_reset);
-    const int8_t wnr = (int8_t)get_winner(T.sw);
-    STAMP(4);
-
-    // terminal observation for gymnasium's info["final_observation"], staged in LDS and stored
-    // with everything else at the end
-    const bool want_final = S.autoreset && S.final_obs != nullptr && !abl(ABL_FINAL);
-    const uint64_t fin = __ballot(ended && want_final);
-    if (__any(ended && want_final)) encode_row(T, B.frows, L);  // rows of other lanes are not stored
-    const int fin_moves = get_moves(T.sw);
-    const float ep_add = (valid && o.term) ? final_reward_p0(T) : 0.0f;
-    STAMP(5);
-    bool pool_dirty = false;
-    if (ended && S.autoreset && !abl(ABL_RESET))
-        autoreset_table(T, A, t, pool, &B.rows[lane * kScratchStride], mtx, o, pool_dirty);
-    STAMP(6);
-    wave_lds_sync();  // deal scratch (rows) free again
-
-    // observation + mask of the current state, block stores
-    if (!abl(ABL_ENCODE)) encode_row(T, B.rows, L);
-    B.mask[lane] = o.mask;
-    STAMP(7);
-    wave_lds_sync();
-    STAMP(8);
-    if (!abl(ABL_STORE)) {
-        if (!abl(ABL_OBS_STORE)) store_obs_block(B.rows, rows, S.obs + (size_t)t0 * kObsDim);
-        STAMP(9);
-        if (!abl(ABL_MASK_STORE)) store_mask_block(B.mask, B.mbits, rows, S.mask + (size_t)t0 * 45);
-    }
-    store_final_rows(B.frows, fin, S.final_obs, t0);
-    STAMP(10);
-    if (valid && o.term) {  // no-return atomics: nothing to wait for
-        if (S.ep_return) unsafeAtomicAdd(&S.ep_return[t], ep_add);
-        if (S.ep_count) atomicAdd(&S.ep_count[t], 1u);
-    }
-    // move_count above 255 (crafted states only) does not fit the byte staging: patch it after
-    // this wave's block stores of the same dwords have left
-    const bool patch = valid && get_moves(T.sw) > 255;
-    const bool fpatch = ended && want_final && fin_moves > 255;
-    if (__any(patch || fpatch)) {
-        __builtin_amdgcn_s_waitcnt(0);
-        if (patch) S.obs[(size_t)t * kObsDim + 295] = get_moves(T.sw);
-        if (fpatch) S.final_obs[(size_t)t * kObsDim + 295] = fin_moves;
-    }
-    store_step_info(S, A.n, t, valid, o.flags);
-    if (valid) {
-        if (!abl(ABL_SMALL_OUT)) {
-            S.reward[t] = o.reward;
-            S.terminated[t] = o.term ? 1 : 0;
-            S.flags[t] = (uint8_t)o.flags;
-            if (S.winner) S.winner[t] = wnr;
-        }
-        if (S.next_actions) {
-            const uint64_t ply = S.ply + (S.ply_base ? *S.ply_base : 0ull);
-            S.next_actions[t] = policy_action(S.policy, o.mask, T, L, S.policy_seed, (uint64_t)(S.table0 + t), ply);
-        }
-        if (!abl(ABL_TAB_STORE)) store_tab(T, A, t, o.mask, Tb.mtag);
-        if (pool_dirty) store_pool(A, t, pool);
-    }
-    STAMP(11);
-}
-
 // K consecutive env steps of every table with the device uniform-random policy: exactly K
-// k_step launches with next_actions fed back as the next launch's actions (plies ply ..
+// spl_step launches with next_actions fed back as the next launch's actions (plies ply ..
 // ply+K-1), without the launch boundaries.  The table state stays in registers; each step's
 // block stores are issued and left to drain while the wave computes the next step, and the
 // next step's deck-card / token-table gathers are issued a whole step ahead.  Step k's outputs
@@ -2179,7 +1991,7 @@ __global__ __launch_bounds__(64) void k_rollout(KArena A, KTables Tb, KStep S, i
         const uint64_t fin = __ballot(valid && o.term && want_final);
         if (__any(valid && o.term && want_final)) encode_row(T, L.frows, L);  // rows of other lanes are not stored
         const int fin_moves = get_moves(T.sw);
-        if (valid && o.term) {  // per termination, as k_step (same float rounding)
+        if (valid && o.term) {  // per termination, as step_ws (same float rounding)
             if (S.ep_return) unsafeAtomicAdd(&S.ep_return[t], final_reward_p0(T));
             if (S.ep_count) atomicAdd(&S.ep_count[t], 1u);
         }
@@ -2208,7 +2020,7 @@ __global__ __launch_bounds__(64) void k_rollout(KArena A, KTables Tb, KStep S, i
         store_mask_block(L.mask, L.mbits, rows, S.mask + blk * 45 + (size_t)t0 * 45);
         int32_t *fobs = want_final ? S.final_obs + blk * kObsDim : nullptr;
         if (want_final) store_final_rows(L.frows, fin, fobs, t0);
-        if (!split && __any(patch || fpatch)) {  // move_count > 255: crafted states only (see k_step)
+        if (!split && __any(patch || fpatch)) {  // move_count > 255 (crafted states only) does not fit the byte staging: patched after the block stores
             __builtin_amdgcn_s_waitcnt(0);
             if (patch) obs[(size_t)t * kObsDim + 295] = get_moves(T.sw);
             if (fpatch) fobs[(size_t)t * kObsDim + 295] = fin_moves;
@@ -2349,7 +2161,7 @@ __device__ __forceinline__ void ws_sync() {
 // while the rules wave evaluates the legal mask of the new state (engine legal_moves,
 // envs/splendor_env.py:81) and stores the masks, small outputs, next action and state.  The
 // output wave also stages the constant tables while the rules wave's state loads
-// are in flight.  (Terminal rows written per lane by the rules wave instead: 27.5 -> 29.0 us.)  Same outputs, bit for bit, as k_step (the GPU parity suite runs through it).
+// are in flight.  (Terminal rows written per lane by the rules wave instead: 27.5 -> 29.0 us.)
 // The TAIL wave (round 6; k_step_wst_<P>p): a third wave per 64 tables takes the legal mask of the new
 // state (engine legal_moves, envs/splendor_env.py:81), the mask block, the fused policy's next action
 // and the legal-mask cache entry off the rules wave's tail; hand-off 2 (rules -> output: row halves
@@ -2358,8 +2170,7 @@ __device__ __forceinline__ void ws_sync() {
 // Same outputs either way.  Measured alternating on one box (profiles/r06/stepab_r06g_h.txt, graph
 // events per step): 16 384 tables 17.4 -> 14.7 us with the tail wave; 65 536 tables 22.4 -> 22.9 us
 // (four workgroups per CU: 12 waves share the SIMDs and the LDS) — so spl_step picks it by grid size
-// (spl_ctx_set_step_tail: auto = at most ctx->step_tail_blocks workgroups).  Its rows leave as sc0 nt sc1
-// stores (SPL_STEP_TAIL_NT): 14.8 -> 12.8 us at 16 384 tables.
+// (spl_ctx_set_step_tail: auto = at most ctx->step_tail_blocks workgroups).  Row store policy: kStepRowCpol.
 
 template <int P>
 struct __align__(16) StepWsLDS : Consts {
@@ -2406,6 +2217,43 @@ __device__ __forceinline__ bool step_wait(const uint32_t *p) {
     }
 }
 
+// The tail of a step, by whichever wave of step_ws takes the new state's legal mask.
+// A lane's step mask with the deferred evaluation done (kMaskDeferred: engine legal_moves of the new state;
+// reset tables carry the fresh deal's, terminal ones none).  `ablated`: what an ABL_LEGAL_POST build takes instead.
+template <int P>
+__device__ __forceinline__ uint64_t resolved_mask(uint64_t m, const Tab<P> &T, const Consts &L, uint64_t ablated = 0ull) {
+    if (m & kMaskDeferred) m = abl(ABL_LEGAL_POST) ? ablated : legal_of(T, L);
+    return m;
+}
+// the wave's mask block, plain stores (kStepRowCpol's comment)
+template <int P>
+__device__ __forceinline__ void store_step_mask(StepWsLDS<P> &L, const KStep &S, uint64_t m, int t0, int rows) {
+    L.mask[lane_id()] = m;
+    wave_lds_sync();
+    if (!abl(ABL_MASK_STORE)) store_mask_block<false>(L.mask, L.mbits, rows, S.mask + (size_t)t0 * 45);
+}
+// the fused policy's action on the stored state
+template <int P>
+__device__ __forceinline__ void store_next_action(const KStep &S, const Consts &L, const Tab<P> &T, uint64_t m, int t) {
+    if (S.next_actions) {
+        const uint64_t ply = S.ply + (S.ply_base ? *S.ply_base : 0ull);
+        S.next_actions[t] = policy_action(S.policy, m, T, L, S.policy_seed, (uint64_t)(S.table0 + t), ply);
+    }
+}
+// Publish m as the legal mask of the state the rules wave stores (tail and output wave): the mask block, the
+// next action and the legal-mask cache entry.  The rules wave (kShape 0) ends in store_tab instead, after its
+// small outputs.
+template <int P>
+__device__ __forceinline__ void publish_mask(StepWsLDS<P> &L, const KArena &A, const KTables &Tb, const KStep &S,
+                                             const Tab<P> &T, uint64_t m, int t0, int rows, bool valid) {
+    const int t = t0 + lane_id();
+    store_step_mask(L, S, m, t0, rows);
+    if (valid) {
+        store_next_action(S, L, T, m, t);
+        store_legal(A, t, m, Tb.mtag);
+    }
+}
+
 // kShape: 0 two waves (the rules wave takes the new state's mask), 1 three waves (the TAIL wave takes
 // it), 2 two waves with the OUTPUT wave taking it in the middle of its row-block stores (k_step_wso)
 template <int P, int kShape>
@@ -2424,7 +2272,7 @@ __device__ __forceinline__ void step_ws(StepWsLDS<P> &L, KArena A, KTables Tb, K
     STAMP(0);
     if (kStepTail && rules_wave && lane == 0) L.halves = 0u;  // read only after hand-off 1
     if (rules_wave) {
-        __builtin_amdgcn_s_setprio(SPL_WS_PRIO);  // as in the rollout: 27.9 -> 27.3 us
+        __builtin_amdgcn_s_setprio(1);  // as in the rollout: 27.9 -> 27.3 us
         Tab<P> T;
         int action = 0;
         Deal pool = empty_deal();
@@ -2491,12 +2339,10 @@ __device__ __forceinline__ void step_ws(StepWsLDS<P> &L, KArena A, KTables Tb, K
         STAMP(7);
         STAMPV(9, __popcll(fin_all) | (__popcll(__ballot((o.mask & kMaskDeferred) != 0)) << 8));
         if (kRulesMask) {
-            if (o.mask & kMaskDeferred) o.mask = abl(ABL_LEGAL_POST) ? (uint64_t)action : legal_of(T, L);
+            o.mask = resolved_mask(o.mask, T, L, (uint64_t)action);
             STAMP(5);
             // masks and small outputs leave from this wave while the output wave streams the rows
-            L.mask[lane] = o.mask;
-            wave_lds_sync();
-            if (!abl(ABL_MASK_STORE)) store_mask_block<false, SPL_STEP_MASK_CPOL>(L.mask, L.mbits, rows, S.mask + (size_t)t0 * 45);
+            store_step_mask(L, S, o.mask, t0, rows);
         }
         STAMP(8);
         store_step_info(S, A.n, t, valid, o.flags);
@@ -2512,10 +2358,7 @@ __device__ __forceinline__ void step_ws(StepWsLDS<P> &L, KArena A, KTables Tb, K
             if (!kRulesMask) {
                 store_words(T, A, t);  // the legal-mask cache entry is the tail / output wave's
             } else {
-                if (S.next_actions) {
-                    const uint64_t ply = S.ply + (S.ply_base ? *S.ply_base : 0ull);
-                    S.next_actions[t] = policy_action(S.policy, o.mask, T, L, S.policy_seed, (uint64_t)(S.table0 + t), ply);
-                }
+                store_next_action(S, L, T, o.mask, t);
                 store_tab(T, A, t, o.mask, Tb.mtag);  // o.mask: legal_moves of the stored (stepped, autoreset) state
             }
             if (pool_dirty) store_pool(A, t, pool);
@@ -2540,10 +2383,7 @@ __device__ __forceinline__ void step_ws(StepWsLDS<P> &L, KArena A, KTables Tb, K
         STAMP(4);
         STAMP(5);
         uint64_t m = 0ull;  // kOMask: the new state's legal mask, evaluated between the row stores
-        auto mask_now = [&]() {
-            m = L.omask[lane];
-            if (m & kMaskDeferred) m = abl(ABL_LEGAL_POST) ? 0ull : legal_of(T, L);
-        };
+        auto mask_now = [&]() { m = resolved_mask(L.omask[lane], T, L); };
         if (compact) {
             store_obs_u8_block(L.rows, rows, S.obs_u8 + (size_t)t0 * kObsU8);
             if (kOMask) mask_now();
@@ -2551,83 +2391,58 @@ __device__ __forceinline__ void step_ws(StepWsLDS<P> &L, KArena A, KTables Tb, K
             if (abl(ABL_OBS_STORE)) {
                 if (kOMask) mask_now();
             } else if (kOMask) {
-                store_obs_block_mid<SPL_STEP_OBS_NT>(L.rows, rows, S.obs + (size_t)t0 * kObsDim, mask_now);
-            } else if (!kStepTail && SPL_STEP_BOTH_NT && S.obs_u8) {  // A/B: with the compact copy (the dual step's
-                // opponent step, whose int32 rows go back to the caller and are not read on the device) as NT rows
-                store_obs_block<64, true>(L.rows, rows, S.obs + (size_t)t0 * kObsDim);
-            } else if (!kStepTail && SPL_STEP_WS_SPLIT != 0) {  // A/B: half the block NT (SPL_ROLL_CPOL), half plain
-                store_obs_block_mid<SPL_STEP_WS_SPLIT == 1, NoOp, SPL_STEP_WS_SPLIT == 2>(L.rows, rows, S.obs + (size_t)t0 * kObsDim, NoOp());
+                store_obs_block_mid(L.rows, rows, S.obs + (size_t)t0 * kObsDim, mask_now);
             } else {
-                constexpr int kCp = kStepTail ? (SPL_STEP_TAIL_CPOL != -3 ? SPL_STEP_TAIL_CPOL : stream_cpol(SPL_STEP_TAIL_NT))
-                                              : (SPL_STEP_OBS_NT ? SPL_ROLL_CPOL : SPL_STEP_WS_CPOL);
-                store_obs_block<64, false, kCp>(L.rows, rows, S.obs + (size_t)t0 * kObsDim);
+                store_obs_block<64, false, kStepRowCpol>(L.rows, rows, S.obs + (size_t)t0 * kObsDim);
             }
             if (S.obs_u8)  // both outputs: the compact copy of the same rows (a fused actor's input)
                 store_u8_from_rows(L.rows, rows, S.obs_u8 + (size_t)t0 * kObsU8, valid ? (uint32_t)get_moves(T.sw) >> 8 : 0u);
         }
         STAMP(6);
-        if (kOMask) {  // the mask block, the fused policy's action and the legal-mask cache entry
-            L.mask[lane] = m;
-            wave_lds_sync();
-            if (!abl(ABL_MASK_STORE)) store_mask_block<false, SPL_STEP_MASK_CPOL>(L.mask, L.mbits, rows, S.mask + (size_t)t0 * 45);
-            if (valid) {
-                if (S.next_actions) {
-                    const uint64_t ply = S.ply + (S.ply_base ? *S.ply_base : 0ull);
-                    S.next_actions[t] = policy_action(S.policy, m, T, L, S.policy_seed, (uint64_t)(S.table0 + t), ply);
-                }
-                store_legal(A, t, m, Tb.mtag);  // m: legal_moves of the state the rules wave stores
-            }
-        }
+        if (kOMask) publish_mask(L, A, Tb, S, T, m, t0, rows, valid);
         if (!compact && __any(valid && get_moves(T.sw) > 255)) {  // patch after this wave's block stores of the same dwords
             __builtin_amdgcn_s_waitcnt(0);
             if (valid && get_moves(T.sw) > 255) S.obs[(size_t)t * kObsDim + 295] = get_moves(T.sw);
         }
         STAMP(7);
     } else if (kStepTail) {
-        // the TAIL wave: from hand-off 1 on, the new state's legal mask (engine legal_moves, deferred
-        // lanes only: reset tables carry the fresh deal's, terminal ones none), the mask block, the fused
-        // policy's next action and the legal-mask cache entry
+        // the TAIL wave: from hand-off 1 on, the new state's legal mask and everything that hangs on it
         ws_sync();  // hand-off 1
         Tab<P> T;
 #pragma unroll
         for (int w = 0; w < kW; ++w) set_tab_word(T, w, L.st[w][lane]);
-        uint64_t m = L.omask[lane];
-        if (m & kMaskDeferred) m = abl(ABL_LEGAL_POST) ? 0ull : legal_of(T, L);
-        L.mask[lane] = m;
-        wave_lds_sync();
-        if (!abl(ABL_MASK_STORE)) store_mask_block<false, SPL_STEP_MASK_CPOL>(L.mask, L.mbits, rows, S.mask + (size_t)t0 * 45);
-        if (valid) {
-            if (S.next_actions) {
-                const uint64_t ply = S.ply + (S.ply_base ? *S.ply_base : 0ull);
-                S.next_actions[t] = policy_action(S.policy, m, T, L, S.policy_seed, (uint64_t)(S.table0 + t), ply);
-            }
-            store_legal(A, t, m, Tb.mtag);  // m: legal_moves of the state the rules wave stores
-        }
+        publish_mask(L, A, Tb, S, T, resolved_mask(L.omask[lane], T, L), t0, rows, valid);
     }
 }
 
-// one kernel name per player count and shape (see RolloutKernel)
-template <int P, int kShape>
-struct StepWsKernel;
-#define SPL_STEP_WS_KERNEL(NAME, P_, SHAPE_)                                                    \
-    __global__ __launch_bounds__(SHAPE_ == 1 ? 192 : 128) void NAME(KArena A, KTables Tb, KStep S) { \
-        __shared__ StepWsLDS<P_> L;                                                              \
-        step_ws<P_, SHAPE_>(L, A, Tb, S);                                                        \
-    }                                                                                            \
-    template <>                                                                                  \
-    struct StepWsKernel<P_, SHAPE_> {                                                            \
-        static constexpr void (*fn)(KArena, KTables, KStep) = NAME;                              \
-    };
-SPL_STEP_WS_KERNEL(k_step_ws_2p, 2, 0)
-SPL_STEP_WS_KERNEL(k_step_ws_3p, 3, 0)
-SPL_STEP_WS_KERNEL(k_step_ws_4p, 4, 0)
-SPL_STEP_WS_KERNEL(k_step_wst_2p, 2, 1)
-SPL_STEP_WS_KERNEL(k_step_wst_3p, 3, 1)
-SPL_STEP_WS_KERNEL(k_step_wst_4p, 4, 1)
-SPL_STEP_WS_KERNEL(k_step_wso_2p, 2, 2)
-SPL_STEP_WS_KERNEL(k_step_wso_3p, 3, 2)
-SPL_STEP_WS_KERNEL(k_step_wso_4p, 4, 2)
-#undef SPL_STEP_WS_KERNEL
+// spl_step's kernels, one line each: X(name, players, shape), in the order of kStepKernels ([shape][players - 2]).
+// One kernel name per player count and shape (see SPL_ROLLOUT_KERNELS).
+#define SPL_STEP_KERNELS(X) \
+    X(k_step_ws_2p, 2, 0)   \
+    X(k_step_ws_3p, 3, 0)   \
+    X(k_step_ws_4p, 4, 0)   \
+    X(k_step_wst_2p, 2, 1)  \
+    X(k_step_wst_3p, 3, 1)  \
+    X(k_step_wst_4p, 4, 1)  \
+    X(k_step_wso_2p, 2, 2)  \
+    X(k_step_wso_3p, 3, 2)  \
+    X(k_step_wso_4p, 4, 2)
+#define SPL_STEP_THREADS(SHAPE_) (SHAPE_ == 1 ? 192 : 128)
+#define X(NAME, P_, SHAPE_)                                                                           \
+    __global__ __launch_bounds__(SPL_STEP_THREADS(SHAPE_)) void NAME(KArena A, KTables Tb, KStep S) { \
+        __shared__ StepWsLDS<P_> L;                                                                   \
+        step_ws<P_, SHAPE_>(L, A, Tb, S);                                                             \
+    }
+SPL_STEP_KERNELS(X)
+#undef X
+struct StepKernel {
+    void (*fn)(KArena, KTables, KStep);
+    int threads;  // per workgroup of 64 tables
+};
+#define X(NAME, P_, SHAPE_) {NAME, SPL_STEP_THREADS(SHAPE_)},
+static const StepKernel kStepKernels[3 * 3] = {SPL_STEP_KERNELS(X)};
+#undef X
+#undef SPL_STEP_THREADS
 
 // Rollout-store delegation (rollout_ws<P, 64, true>, spl_ctx_set_rollout_delegation).  The
 // XCCs of an MI355X do not drain stores equally fast: with the rollout store's own write pattern
@@ -2833,7 +2648,7 @@ __device__ __forceinline__ void pt_store_task(const uint8_t *slot, uint8_t *rows
     unstage_state(slot, T);
     encode_row(T, rows_lds, C);
     wave_lds_sync();
-    store_obs_block<64, kRollNT>(rows_lds, 64, dst);
+    store_obs_block<64, true>(rows_lds, 64, dst);
     wave_lds_sync();  // the block's LDS reads are done before the next task's rows land
 }
 // consumer (the partner team's output wave): `v` = the flag of the partner's slot cseq; if it is READY,
@@ -3147,7 +2962,7 @@ __device__ __forceinline__ void rollout_ws(LdsT &L, KArena A, KTables Tb, KStep 
     WSHWID(sid, rules_wave ? 0 : 1);
     // the rules wave is the critical path: it wins issue arbitration against the CU's output
     // waves (rollout store 1134 -> 1103 us per launch on one box; 1 and 3 measure the same)
-    if (rules_wave) __builtin_amdgcn_s_setprio(SPL_WS_PRIO);
+    if (rules_wave) __builtin_amdgcn_s_setprio(1);
 #ifdef SPL_STAMPS
     const uint64_t clk0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -3217,7 +3032,7 @@ __device__ __forceinline__ void rollout_ws(LdsT &L, KArena A, KTables Tb, KStep 
                     store_row_direct(T, L, S.final_obs + (blk + (size_t)t) * kObsDim);
                 }
             }
-            const float ep_add = (valid && o.term) ? final_reward_p0(T) : 0.0f;  // per termination, as k_step
+            const float ep_add = (valid && o.term) ? final_reward_p0(T) : 0.0f;  // per termination, as step_ws
             if constexpr (kDealer) {
                 if (!dealer_step<P>(L.dl, T, A, t, valid, valid && o.term && S.autoreset, S.autoreset != 0, pool,
                                     pool_dirty, my_req, infl, pool_stale, o)) {
@@ -3373,10 +3188,7 @@ __device__ __forceinline__ void rollout_ws(LdsT &L, KArena A, KTables Tb, KStep 
                 int32_t *fobs = S.final_obs + blk * kObsDim;
                 for (int idx = 0; fin; fin &= fin - 1, ++idx) {
                     const int r = __ffsll((unsigned long long)fin) - 1;
-                    if constexpr (per_step && SPL_ROLL_SMALL_NT)
-                        store_row_columns_nt<P>(&L.tst[b][idx][0], 1, L, crc, fobs + (size_t)(t0 + r) * kObsDim);
-                    else
-                        store_row_columns<P>(&L.tst[b][idx][0], 1, L, crc, fobs + (size_t)(t0 + r) * kObsDim);
+                    store_row_columns<P>(&L.tst[b][idx][0], 1, L, crc, fobs + (size_t)(t0 + r) * kObsDim);
                 }
             }
             const bool big_moves = __any(valid && get_moves(T.sw) > 255);
@@ -3409,7 +3221,7 @@ __device__ __forceinline__ void rollout_ws(LdsT &L, KArena A, KTables Tb, KStep 
             } else if (deleg_now) {
                 const int j = k / dl.every;
                 if (big_moves) {  // a patched row: stored here, the partner skips the task
-                    store_obs_block<TPW, kRollNT>(L.rows, rows, obs + (size_t)t0 * kObsDim);
+                    store_obs_block<TPW, true>(L.rows, rows, obs + (size_t)t0 * kObsDim);
                     flag_store(ready_flag(j), dl.epoch << 1 | 1u);
                 } else {
                     stage_state(T, slot_of(j));
@@ -3418,44 +3230,20 @@ __device__ __forceinline__ void rollout_ws(LdsT &L, KArena A, KTables Tb, KStep 
                     pend_k = k;
                 }
             } else if (abl(ABL_OBS_STORE)) {
-            } else if (per_step) {
-                store_obs_block<TPW, kRollNT>(L.rows, rows, obs + (size_t)t0 * kObsDim);
-            } else {
-                store_obs_block<TPW, false>(L.rows, rows, obs + (size_t)t0 * kObsDim);
+            } else {  // per-step blocks through the NT stream, in-place ones plain (kRollCpol's comment)
+                store_obs_block<TPW, per_step>(L.rows, rows, obs + (size_t)t0 * kObsDim);
             }
             WSSTAMP(2, k);
-            if (abl(ABL_MASK_STORE)) {
-            } else if (per_step) {
-                store_mask_block<kRollNT>(L.mask[b], L.mbits, rows, S.mask + blk * 45 + (size_t)t0 * 45);
-            } else {
-                store_mask_block<false>(L.mask[b], L.mbits, rows, S.mask + blk * 45 + (size_t)t0 * 45);
-            }
+            if (!abl(ABL_MASK_STORE)) store_mask_block<per_step>(L.mask[b], L.mbits, rows, S.mask + blk * 45 + (size_t)t0 * 45);
             const uint32_t sm = L.small[b][lane];
-            if constexpr (per_step && SPL_ROLL_SMALL_NT && SPL_ROLL_CPOL >= 0) {  // A/B: the NT stream's policy
-                const size_t o = blk + (size_t)t0;  // this wave's 64 tables of step k (wave-uniform)
-                const auto rsr = __builtin_amdgcn_make_buffer_rsrc(S.reward + o, (short)0, 256, 0x00020000);
-                const auto rst = __builtin_amdgcn_make_buffer_rsrc(S.terminated + o, (short)0, 64, 0x00020000);
-                const auto rsf = __builtin_amdgcn_make_buffer_rsrc(S.flags + o, (short)0, 64, 0x00020000);
-                if (sm & (1u << 9)) {
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, reward_of_code((sm >> 13) & 7u)), rsr,
-                                                          (t - t0) * 4, 0, SPL_ROLL_CPOL);
-                    __builtin_amdgcn_raw_buffer_store_b8((uint8_t)((sm >> 8) & 1u), rst, t - t0, 0, SPL_ROLL_CPOL);
-                    __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(sm & 0xFFu), rsf, t - t0, 0, SPL_ROLL_CPOL);
-                }
-                if (S.winner) {
-                    const auto rsw = __builtin_amdgcn_make_buffer_rsrc(S.winner + o, (short)0, 64, 0x00020000);
-                    if (sm & (1u << 9))
-                        __builtin_amdgcn_raw_buffer_store_b8((uint8_t)((int)((sm >> 10) & 7u) - 1), rsw, t - t0, 0, SPL_ROLL_CPOL);
-                }
-            }
             if (sm & (1u << 9)) {  // valid lane: the rules wave's small outputs and episode statistics
-                if constexpr (!(per_step && SPL_ROLL_SMALL_NT && SPL_ROLL_CPOL >= 0) && !(SPL_ABL & ABL_SMALL_OUT)) {
+                if (!abl(ABL_SMALL_OUT)) {
                     S.reward[blk + t] = reward_of_code((sm >> 13) & 7u);
                     S.terminated[blk + t] = (uint8_t)((sm >> 8) & 1u);
                     S.flags[blk + t] = (uint8_t)(sm & 0xFFu);
                     if (S.winner) S.winner[blk + t] = (int8_t)((int)((sm >> 10) & 7u) - 1);
                 }
-                if (sm & (1u << 18)) {  // same per-table order and float rounding as k_step
+                if (sm & (1u << 18)) {  // same per-table order and float rounding as step_ws
                     if (S.ep_return) unsafeAtomicAdd(&S.ep_return[t], ep_of_code((sm >> 16) & 3u));
                     if (S.ep_count) atomicAdd(&S.ep_count[t], 1u);
                 }
@@ -3512,7 +3300,7 @@ __device__ __forceinline__ void rollout_ws(LdsT &L, KArena A, KTables Tb, KStep 
                 unstage_state(slot_of(j), T);
                 encode_row(T, L.rows, L);
                 wave_lds_sync();
-                store_obs_block<TPW, kRollNT>(L.rows, 64, S.obs + ((size_t)k * (size_t)A.n + pt0) * kObsDim);
+                store_obs_block<TPW, true>(L.rows, 64, S.obs + ((size_t)k * (size_t)A.n + pt0) * kObsDim);
                 wave_lds_sync();  // the block's LDS reads are done before the next task's rows land
             }
         }
@@ -3526,7 +3314,7 @@ __device__ __forceinline__ void rollout_ws(LdsT &L, KArena A, KTables Tb, KStep 
                 unstage_state(slot_of(j), T);
                 encode_row(T, L.rows, L);
                 wave_lds_sync();
-                store_obs_block<TPW, kRollNT>(L.rows, 64, S.obs + ((size_t)k * (size_t)A.n + t0) * kObsDim);
+                store_obs_block<TPW, true>(L.rows, 64, S.obs + ((size_t)k * (size_t)A.n + t0) * kObsDim);
                 wave_lds_sync();
             }
         }
@@ -3545,52 +3333,6 @@ __device__ __forceinline__ void rollout_ws(LdsT &L, KArena A, KTables Tb, KStep 
     }
 }
 
-// One kernel name per instantiation: a rocprofv3 --stats summary names kernels by the text before
-// the template argument list when it truncates, so the per-step store (the headline), the in-place
-// variant and the 32-tables-per-workgroup shapes must differ there to be separate rows.
-template <int P, int TPW, bool kStore>
-struct RolloutKernel;
-#define SPL_ROLLOUT_KERNEL(NAME, P_, TPW_, ST_)                                                               \
-    __global__ __launch_bounds__(128) void NAME(KArena A, KTables Tb, KStep S, int K, int refill, int deleg) { \
-        __shared__ WsLDS<P_> L;                                                                                \
-        rollout_ws<P_, TPW_, ST_>(L, A, Tb, S, K, refill, deleg);                                              \
-    }                                                                                                          \
-    template <>                                                                                                \
-    struct RolloutKernel<P_, TPW_, ST_> {                                                                      \
-        static constexpr void (*fn)(KArena, KTables, KStep, int, int, int) = NAME;                             \
-    };
-SPL_ROLLOUT_KERNEL(k_rollout_store_2p, 2, 64, true)
-SPL_ROLLOUT_KERNEL(k_rollout_store_3p, 3, 64, true)
-SPL_ROLLOUT_KERNEL(k_rollout_store_4p, 4, 64, true)
-SPL_ROLLOUT_KERNEL(k_rollout_store_half_2p, 2, 32, true)
-SPL_ROLLOUT_KERNEL(k_rollout_store_half_3p, 3, 32, true)
-SPL_ROLLOUT_KERNEL(k_rollout_store_half_4p, 4, 32, true)
-SPL_ROLLOUT_KERNEL(k_rollout_inplace_2p, 2, 64, false)
-SPL_ROLLOUT_KERNEL(k_rollout_inplace_3p, 3, 64, false)
-SPL_ROLLOUT_KERNEL(k_rollout_inplace_4p, 4, 64, false)
-SPL_ROLLOUT_KERNEL(k_rollout_inplace_half_2p, 2, 32, false)
-SPL_ROLLOUT_KERNEL(k_rollout_inplace_half_3p, 3, 32, false)
-SPL_ROLLOUT_KERNEL(k_rollout_inplace_half_4p, 4, 32, false)
-#undef SPL_ROLLOUT_KERNEL
-// the dealer variants (three waves, 64 tables per workgroup; grids of at most two workgroups per CU)
-template <int P, bool kStore>
-struct RolloutDealerKernel;
-#define SPL_DEALER_KERNEL(NAME, P_, ST_)                                                                       \
-    __global__ __launch_bounds__(192) void NAME(KArena A, KTables Tb, KStep S, int K, int refill, int deleg) { \
-        __shared__ WsDealLDS<P_> L;                                                                            \
-        rollout_ws<P_, 64, ST_, true>(L, A, Tb, S, K, refill, deleg);                                          \
-    }                                                                                                          \
-    template <>                                                                                                \
-    struct RolloutDealerKernel<P_, ST_> {                                                                      \
-        static constexpr void (*fn)(KArena, KTables, KStep, int, int, int) = NAME;                             \
-    };
-SPL_DEALER_KERNEL(k_rollout_store_dealer_2p, 2, true)
-SPL_DEALER_KERNEL(k_rollout_store_dealer_3p, 3, true)
-SPL_DEALER_KERNEL(k_rollout_store_dealer_4p, 4, true)
-SPL_DEALER_KERNEL(k_rollout_inplace_dealer_2p, 2, false)
-SPL_DEALER_KERNEL(k_rollout_inplace_dealer_3p, 3, false)
-SPL_DEALER_KERNEL(k_rollout_inplace_dealer_4p, 4, false)
-#undef SPL_DEALER_KERNEL
 
 // The six-wave dealer variant (round 4; k_rollout_*_dealer2_<P>p, 128 tables per workgroup, one
 // workgroup per CU): two dealer-rollout teams (rules, output, dealer wave, 64 tables each) in ONE
@@ -3669,24 +3411,6 @@ __device__ __forceinline__ void rollout_dealer2(WsDeal2LDS<P> &L, KArena A, KTab
     rollout_ws<P, 64, kStore, true, WsDealLDS<P>, 2>(L.team[team], A, Tb, S, K, refill, lead,
                                                       WaveRole{code % 3, 2 * wg_block() + team});
 }
-template <int P, bool kStore>
-struct RolloutDealer2Kernel;
-#define SPL_DEALER2_KERNEL(NAME, P_, ST_)                                                                      \
-    __global__ __launch_bounds__(384) void NAME(KArena A, KTables Tb, KStep S, int K, int refill, int deleg) { \
-        __shared__ WsDeal2LDS<P_> L;                                                                           \
-        rollout_dealer2<P_, ST_>(L, A, Tb, S, K, refill, deleg);                                               \
-    }                                                                                                          \
-    template <>                                                                                                \
-    struct RolloutDealer2Kernel<P_, ST_> {                                                                     \
-        static constexpr void (*fn)(KArena, KTables, KStep, int, int, int) = NAME;                             \
-    };
-SPL_DEALER2_KERNEL(k_rollout_store_dealer2_2p, 2, true)
-SPL_DEALER2_KERNEL(k_rollout_store_dealer2_3p, 3, true)
-SPL_DEALER2_KERNEL(k_rollout_store_dealer2_4p, 4, true)
-SPL_DEALER2_KERNEL(k_rollout_inplace_dealer2_2p, 2, false)
-SPL_DEALER2_KERNEL(k_rollout_inplace_dealer2_3p, 3, false)
-SPL_DEALER2_KERNEL(k_rollout_inplace_dealer2_4p, 4, false)
-#undef SPL_DEALER2_KERNEL
 
 // The quad variant (round 5; k_rollout_*_quad_<P>p, 256 tables per workgroup, one workgroup per CU):
 // four two-wave teams (rules + output wave, 64 tables each) in ONE 512-thread workgroup — the
@@ -3762,24 +3486,68 @@ __device__ __forceinline__ void rollout_quad(WsQuadLDS<P> &L, KArena A, KTables 
     rollout_ws<P, 64, kStore, false, WsLDS<P>, 4>(L.team[team], A, Tb, S, K, refill, lead,
                                                   WaveRole{code & 1, 4 * wg_block() + team});
 }
-template <int P, bool kStore>
-struct RolloutQuadKernel;
-#define SPL_QUAD_KERNEL(NAME, P_, ST_)                                                                         \
-    __global__ __launch_bounds__(512) void NAME(KArena A, KTables Tb, KStep S, int K, int refill, int deleg) { \
-        __shared__ WsQuadLDS<P_> L;                                                                            \
-        rollout_quad<P_, ST_>(L, A, Tb, S, K, refill, deleg);                                                  \
-    }                                                                                                          \
-    template <>                                                                                                \
-    struct RolloutQuadKernel<P_, ST_> {                                                                        \
-        static constexpr void (*fn)(KArena, KTables, KStep, int, int, int) = NAME;                             \
-    };
-SPL_QUAD_KERNEL(k_rollout_store_quad_2p, 2, true)
-SPL_QUAD_KERNEL(k_rollout_store_quad_3p, 3, true)
-SPL_QUAD_KERNEL(k_rollout_store_quad_4p, 4, true)
-SPL_QUAD_KERNEL(k_rollout_inplace_quad_2p, 2, false)
-SPL_QUAD_KERNEL(k_rollout_inplace_quad_3p, 3, false)
-SPL_QUAD_KERNEL(k_rollout_inplace_quad_4p, 4, false)
-#undef SPL_QUAD_KERNEL
+
+// Every multi-wave rollout kernel, one line each:
+//   X(name, threads per workgroup, tables per workgroup, extra argument, LDS type, body)
+// in the order of kRolloutKernels: [shape - 2][per_step][players - 2], the shapes being
+// spl_ctx_set_rollout_pipeline's 2 two waves, 3 two waves half-populated (32 tables), 4 the three-wave dealer,
+// 5 the six-wave dealer, 6 quad.  (Shape 0, the one-wave k_rollout<P>, takes other arguments and is launched
+// by name.)  One kernel name per instantiation: a rocprofv3 --stats summary names kernels by the text before
+// the template argument list when it truncates, so the per-step store (the headline), the in-place variant
+// and the shapes must differ there to be separate rows.
+// The extra (last) kernel argument, 0 unless every workgroup of the grid is resident at once: the two-wave
+// store's static delegation period, or the partner lead of the one-workgroup-per-CU stores.
+enum RolloutExtra { kExtraNone, kExtraDeleg, kExtraLead };
+#define SPL_ROLLOUT_KERNELS(X)                                                                        \
+    X(k_rollout_inplace_2p, 128, 64, kExtraNone, WsLDS<2>, rollout_ws<2, 64, false>)                  \
+    X(k_rollout_inplace_3p, 128, 64, kExtraNone, WsLDS<3>, rollout_ws<3, 64, false>)                  \
+    X(k_rollout_inplace_4p, 128, 64, kExtraNone, WsLDS<4>, rollout_ws<4, 64, false>)                  \
+    X(k_rollout_store_2p, 128, 64, kExtraDeleg, WsLDS<2>, rollout_ws<2, 64, true>)                    \
+    X(k_rollout_store_3p, 128, 64, kExtraDeleg, WsLDS<3>, rollout_ws<3, 64, true>)                    \
+    X(k_rollout_store_4p, 128, 64, kExtraDeleg, WsLDS<4>, rollout_ws<4, 64, true>)                    \
+    X(k_rollout_inplace_half_2p, 128, 32, kExtraNone, WsLDS<2>, rollout_ws<2, 32, false>)             \
+    X(k_rollout_inplace_half_3p, 128, 32, kExtraNone, WsLDS<3>, rollout_ws<3, 32, false>)             \
+    X(k_rollout_inplace_half_4p, 128, 32, kExtraNone, WsLDS<4>, rollout_ws<4, 32, false>)             \
+    X(k_rollout_store_half_2p, 128, 32, kExtraNone, WsLDS<2>, rollout_ws<2, 32, true>)                \
+    X(k_rollout_store_half_3p, 128, 32, kExtraNone, WsLDS<3>, rollout_ws<3, 32, true>)                \
+    X(k_rollout_store_half_4p, 128, 32, kExtraNone, WsLDS<4>, rollout_ws<4, 32, true>)                \
+    X(k_rollout_inplace_dealer_2p, 192, 64, kExtraNone, WsDealLDS<2>, rollout_ws<2, 64, false, true>) \
+    X(k_rollout_inplace_dealer_3p, 192, 64, kExtraNone, WsDealLDS<3>, rollout_ws<3, 64, false, true>) \
+    X(k_rollout_inplace_dealer_4p, 192, 64, kExtraNone, WsDealLDS<4>, rollout_ws<4, 64, false, true>) \
+    X(k_rollout_store_dealer_2p, 192, 64, kExtraNone, WsDealLDS<2>, rollout_ws<2, 64, true, true>)    \
+    X(k_rollout_store_dealer_3p, 192, 64, kExtraNone, WsDealLDS<3>, rollout_ws<3, 64, true, true>)    \
+    X(k_rollout_store_dealer_4p, 192, 64, kExtraNone, WsDealLDS<4>, rollout_ws<4, 64, true, true>)    \
+    X(k_rollout_inplace_dealer2_2p, 384, 128, kExtraNone, WsDeal2LDS<2>, rollout_dealer2<2, false>)   \
+    X(k_rollout_inplace_dealer2_3p, 384, 128, kExtraNone, WsDeal2LDS<3>, rollout_dealer2<3, false>)   \
+    X(k_rollout_inplace_dealer2_4p, 384, 128, kExtraNone, WsDeal2LDS<4>, rollout_dealer2<4, false>)   \
+    X(k_rollout_store_dealer2_2p, 384, 128, kExtraLead, WsDeal2LDS<2>, rollout_dealer2<2, true>)      \
+    X(k_rollout_store_dealer2_3p, 384, 128, kExtraLead, WsDeal2LDS<3>, rollout_dealer2<3, true>)      \
+    X(k_rollout_store_dealer2_4p, 384, 128, kExtraLead, WsDeal2LDS<4>, rollout_dealer2<4, true>)      \
+    X(k_rollout_inplace_quad_2p, 512, 256, kExtraNone, WsQuadLDS<2>, rollout_quad<2, false>)          \
+    X(k_rollout_inplace_quad_3p, 512, 256, kExtraNone, WsQuadLDS<3>, rollout_quad<3, false>)          \
+    X(k_rollout_inplace_quad_4p, 512, 256, kExtraNone, WsQuadLDS<4>, rollout_quad<4, false>)          \
+    X(k_rollout_store_quad_2p, 512, 256, kExtraLead, WsQuadLDS<2>, rollout_quad<2, true>)             \
+    X(k_rollout_store_quad_3p, 512, 256, kExtraLead, WsQuadLDS<3>, rollout_quad<3, true>)             \
+    X(k_rollout_store_quad_4p, 512, 256, kExtraLead, WsQuadLDS<4>, rollout_quad<4, true>)
+#define X(NAME, THREADS_, TPW_, EXTRA_, LDS_, ...)                                                                  \
+    __global__ __launch_bounds__(THREADS_) void NAME(KArena A, KTables Tb, KStep S, int K, int refill, int extra) { \
+        __shared__ LDS_ L;                                                                                          \
+        __VA_ARGS__(L, A, Tb, S, K, refill, extra);                                                                 \
+    }
+SPL_ROLLOUT_KERNELS(X)
+#undef X
+struct RolloutKernel {
+    const char *name;
+    void (*fn)(KArena, KTables, KStep, int, int, int);
+    int threads, tpw;  // per workgroup: threads, tables
+    RolloutExtra extra;
+};
+#define X(NAME, THREADS_, TPW_, EXTRA_, LDS_, ...) {#NAME, NAME, THREADS_, TPW_, EXTRA_},
+static const RolloutKernel kRolloutKernels[5 * 2 * 3] = {SPL_ROLLOUT_KERNELS(X)};
+#undef X
+static const RolloutKernel &rollout_kernel(int shape, bool per_step, int players) {
+    return kRolloutKernels[((shape - 2) * 2 + (per_step ? 1 : 0)) * 3 + players - 2];
+}
 
 // Explicit reset (SplendorEnv.reset / VectorEnv.reset), then observation + mask of all tables.
 template <int P>
@@ -4077,11 +3845,9 @@ struct spl_ctx_s {
     uint4 *lut;
     int refill_period;
     int refill_fused;  // spl_rollout: refill inside the rollout launch (default) or as a k_refill launch after it
-    int pipeline;      // spl_rollout: 0 one wave per 64 tables, 1 two-wave (auto tables per workgroup), 2 / 3 two-wave at 64 / 32
-    int ws_resident[5];  // k_rollout_store_<P>p: workgroups resident per device (occupancy x CUs), index P
-    int dealer_resident[5];  // k_rollout_store_dealer_<P>p: the same for the three-wave dealer variant
-    int dealer2_resident[5]; // k_rollout_store_dealer2_<P>p: the same for the six-wave dealer variant
-    int quad_resident[5];    // k_rollout_store_quad_<P>p: the same for the quad variant
+    int pipeline;      // spl_rollout's shape: 0 one wave per 64 tables, 1 auto (rollout_shape), 2-6 see SPL_ROLLOUT_KERNELS
+    int resident[7][5];  // [shape 2..6][players]: workgroups of the shape's per-step store kernel resident per
+                         // device (occupancy x CUs)
     int deleg_every;     // spl_rollout per-step store: rollout-store delegation every n-th step (0 = off)
     int partner_lead;    // per-step store partner hand-off lead in steps (0 off, < 0 forced)
     uint32_t mtag;         // legal-mask cache tag of this context's card table (card_table_tag), 1..65535, or 0
@@ -4136,14 +3902,6 @@ static int launch_check() {
 }
 
 static inline unsigned blocks_for(int64_t n) { return (unsigned)((n + 63) / 64); }
-#ifndef SPL_STEP_WAVES
-#define SPL_STEP_WAVES 1
-#endif
-constexpr int kStepWaves = SPL_STEP_WAVES;  // k_step waves per workgroup
-#ifndef SPL_STEP_WS
-#define SPL_STEP_WS 1
-#endif
-constexpr bool kStepWs = SPL_STEP_WS != 0;  // spl_step: two-wave k_step_ws_<P>p (else k_step)
 
 extern "C" {
 
@@ -4266,38 +4024,25 @@ int spl_ctx_create(int device, const int32_t *cards, const int32_t *nobles, spl_
         memcpy(&nrec[i], b, 8);
     }
     HIP_TRY(hipSetDevice(device));
-    int ws_resident[5], dealer_resident[5], dealer2_resident[5], quad_resident[5];
+    int resident[7][5] = {};
     {
         int cus = 0;
         HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-        int occ[5] = {0, 0, 0, 0, 0};
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ[2], RolloutKernel<2, 64, true>::fn, 128, 0));
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ[3], RolloutKernel<3, 64, true>::fn, 128, 0));
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ[4], RolloutKernel<4, 64, true>::fn, 128, 0));
-        for (int q = 0; q < 5; ++q) ws_resident[q] = occ[q] * cus;
-        int docc[5] = {0, 0, 0, 0, 0};
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&docc[2], RolloutDealerKernel<2, true>::fn, 192, 0));
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&docc[3], RolloutDealerKernel<3, true>::fn, 192, 0));
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&docc[4], RolloutDealerKernel<4, true>::fn, 192, 0));
-        for (int q = 0; q < 5; ++q) dealer_resident[q] = docc[q] * cus;
-        int d2occ[5] = {0, 0, 0, 0, 0};
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&d2occ[2], RolloutDealer2Kernel<2, true>::fn, 384, 0));
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&d2occ[3], RolloutDealer2Kernel<3, true>::fn, 384, 0));
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&d2occ[4], RolloutDealer2Kernel<4, true>::fn, 384, 0));
-        for (int q = 0; q < 5; ++q) dealer2_resident[q] = d2occ[q] * cus;
-        int qocc[5] = {0, 0, 0, 0, 0};
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&qocc[2], RolloutQuadKernel<2, true>::fn, 512, 0));
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&qocc[3], RolloutQuadKernel<3, true>::fn, 512, 0));
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&qocc[4], RolloutQuadKernel<4, true>::fn, 512, 0));
-        for (int q = 0; q < 5; ++q) quad_resident[q] = qocc[q] * cus;
+        for (int shape = 2; shape <= 6; ++shape)
+            for (int p = 2; p <= 4; ++p) {
+                const RolloutKernel &k = rollout_kernel(shape, true, p);
+                int occ = 0;
+                HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k.fn, k.threads, 0));
+                resident[shape][p] = occ * cus;
+            }
     }
     spl_ctx_t *c = new spl_ctx_t();
     c->device = device;
     c->mtag = card_table_tag(crec, nrec);
     c->refill_period = 64;
     c->refill_fused = 1;
-    c->deleg_every = SPL_DELEG_EVERY;
-    c->partner_lead = SPL_PARTNER_LEAD;
+    c->deleg_every = kDelegEveryDefault;
+    c->partner_lead = kPartnerLeadDefault;
     c->step_tail = -1;
     {
         int cus = 0;
@@ -4307,10 +4052,7 @@ int spl_ctx_create(int device, const int32_t *cards, const int32_t *nobles, spl_
         c->step_tail_blocks = 3 * (int64_t)cus;
     }
     c->pipeline = 1;
-    memcpy(c->ws_resident, ws_resident, sizeof(ws_resident));
-    memcpy(c->dealer_resident, dealer_resident, sizeof(dealer_resident));
-    memcpy(c->dealer2_resident, dealer2_resident, sizeof(dealer2_resident));
-    memcpy(c->quad_resident, quad_resident, sizeof(quad_resident));
+    memcpy(c->resident, resident, sizeof(resident));
     if (hipMalloc(&c->cards, sizeof(uint4) * 90) != hipSuccess || hipMalloc(&c->nobles, sizeof(uint2) * 10) != hipSuccess ||
         hipMalloc(&c->lut, sizeof(uint4) * kLutEntries) != hipSuccess) {
         spl_ctx_destroy(c);
@@ -4540,30 +4282,16 @@ static KStep kstep(spl_ctx_t *ctx, const spl_step_args_t *a) {
 int spl_step(spl_ctx_t *ctx, spl_arena_t *arena, const spl_step_args_t *a, void *stream) {
     if (int r = check_arena(ctx, arena)) return r;
     if (int r = check_step_args(a)) return r;
-    if (a->obs_u8 && !kStepWs) return fail(SPL_E_ARG, "obs_u8 needs the two-wave step kernel");
     const KStep S = kstep(ctx, a);
     const KArena A = karena(arena);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (kStepWs) {
-        const unsigned blocks = blocks_for(arena->n);
-        // auto: the tail wave up to three workgroups per CU, and for compact-only outputs (obs_u8 without the
-        // int32 rows: a quarter of the row stores, so the rules wave's tail is the longer one)
-        const int shape = ctx->step_tail >= 0 ? ctx->step_tail
-                                              : (((int64_t)blocks <= ctx->step_tail_blocks || a->obs == nullptr) ? 1 : 0);
-        if (shape == 1)
-            DISPATCH_P(arena->players, hipLaunchKernelGGL((StepWsKernel<PP, 1>::fn), dim3(blocks), dim3(192), 0, s, A,
-                                                          ktables(ctx), S))
-        else if (shape == 2)
-            DISPATCH_P(arena->players, hipLaunchKernelGGL((StepWsKernel<PP, 2>::fn), dim3(blocks), dim3(128), 0, s, A,
-                                                          ktables(ctx), S))
-        else
-            DISPATCH_P(arena->players, hipLaunchKernelGGL((StepWsKernel<PP, 0>::fn), dim3(blocks), dim3(128), 0, s, A,
-                                                          ktables(ctx), S))
-    } else {
-        DISPATCH_P(arena->players,
-                   hipLaunchKernelGGL((k_step<PP, kStepWaves>), dim3((unsigned)((arena->n + 64 * kStepWaves - 1) / (64 * kStepWaves))),
-                                      dim3(64 * kStepWaves), 0, s, A, ktables(ctx), S));
-    }
+    const unsigned blocks = blocks_for(arena->n);
+    // auto: the tail wave up to three workgroups per CU, and for compact-only outputs (obs_u8 without the
+    // int32 rows: a quarter of the row stores, so the rules wave's tail is the longer one)
+    const int shape = ctx->step_tail >= 0 ? ctx->step_tail
+                                          : (((int64_t)blocks <= ctx->step_tail_blocks || a->obs == nullptr) ? 1 : 0);
+    const StepKernel &k = kStepKernels[shape * 3 + arena->players - 2];
+    hipLaunchKernelGGL(k.fn, dim3(blocks), dim3(k.threads), 0, s, A, ktables(ctx), S);
     if (int r = launch_check()) return r;
     arena->steps += 1;
     if (a->autoreset && ctx->refill_period > 0 && arena->steps % ctx->refill_period == 0)
@@ -4571,58 +4299,38 @@ int spl_step(spl_ctx_t *ctx, spl_arena_t *arena, const spl_step_args_t *a, void 
     return SPL_OK;
 }
 
-// The rollout kernel shape: tables per workgroup of the two-wave rollout (0 = the one-wave
-// k_rollout), or kDealerShape / kDealer2Shape for the three- / six-wave dealer variants.  Auto
-// (pipeline 1): the six-wave dealer variant when every 128-table workgroup is resident at once (one
+// whether every workgroup of the shape's grid over n tables is resident at once
+static bool rollout_fits(const spl_ctx_t *ctx, int shape, int32_t n, int32_t players) {
+    const int tpw = rollout_kernel(shape, true, players).tpw;
+    return ((int64_t)n + tpw - 1) / tpw <= ctx->resident[shape][players];
+}
+
+// The rollout kernel shape (0 the one-wave k_rollout, 2-6 see SPL_ROLLOUT_KERNELS).  Auto (pipeline 1):
+// the six-wave dealer variant when every 128-table workgroup is resident at once (one
 // per CU, e.g. C4's 32 768 tables per GPU: 1 120-1 137 against 1 166-1 172 us per 128-step launch
 // for the three-wave one, alternating on one box, profiles/r04/c4ab_r04b.txt), else the three-wave
 // one when it fits, else (2 players) the quad kernel when every 256-table workgroup is resident, else
 // two waves at 64 tables per workgroup.
-constexpr int kDealerShape = -1, kDealer2Shape = -2, kQuadShape = -3;
-static int rollout_tpw(const spl_ctx_t *ctx, int32_t n, int32_t players) {
-    if (ctx->pipeline == 2) return 64;
-    if (ctx->pipeline == 3) return 32;
-    if (ctx->pipeline == 4) return kDealerShape;
-    if (ctx->pipeline == 5) return kDealer2Shape;
-    if (ctx->pipeline == 6) return kQuadShape;
-    if (ctx->pipeline == 1) {  // auto: the six-wave dealer (SIMD-aware roles, -3.5 % on C4's share), else three-wave
-        if ((int64_t)((n + 127) / 128) <= ctx->dealer2_resident[players]) return kDealer2Shape;
-        if ((int64_t)blocks_for(n) <= ctx->dealer_resident[players]) return kDealerShape;
-        // 2 players up to one quad workgroup per CU (the headline's 65 536 tables): the quad kernel with its
-        // partner hand-off, 1 959-1 983 against 2 008-2 031 us per 128-step launch for the two-wave kernel,
-        // alternating on one box (profiles/r05/headline_quad_ab_r05h.txt); 3-4 players keep the two-wave
-        if (players == 2 && (int64_t)((n + 255) / 256) <= ctx->quad_resident[players]) return kQuadShape;
-        return 64;
-    }
-    return 0;
+static int rollout_shape(const spl_ctx_t *ctx, int32_t n, int32_t players) {
+    if (ctx->pipeline != 1) return ctx->pipeline;
+    // auto: the six-wave dealer (SIMD-aware roles, -3.5 % on C4's share), else three-wave
+    if (rollout_fits(ctx, 5, n, players)) return 5;
+    if (rollout_fits(ctx, 4, n, players)) return 4;
+    // 2 players up to one quad workgroup per CU (the headline's 65 536 tables): the quad kernel with its
+    // partner hand-off, 1 959-1 983 against 2 008-2 031 us per 128-step launch for the two-wave kernel,
+    // alternating on one box (profiles/r05/headline_quad_ab_r05h.txt); 3-4 players keep the two-wave
+    if (players == 2 && rollout_fits(ctx, 6, n, players)) return 6;
+    return 2;
 }
 
 const char *spl_rollout_kernel_name(spl_ctx_t *ctx, int32_t n, int32_t players, int32_t per_step_outputs) {
-    static const char *const names[2][2][3] = {
-        {{"k_rollout_inplace_2p", "k_rollout_inplace_3p", "k_rollout_inplace_4p"},
-         {"k_rollout_inplace_half_2p", "k_rollout_inplace_half_3p", "k_rollout_inplace_half_4p"}},
-        {{"k_rollout_store_2p", "k_rollout_store_3p", "k_rollout_store_4p"},
-         {"k_rollout_store_half_2p", "k_rollout_store_half_3p", "k_rollout_store_half_4p"}}};
     static const char *const one_wave[3] = {"k_rollout<2>", "k_rollout<3>", "k_rollout<4>"};
-    static const char *const dealer[2][3] = {
-        {"k_rollout_inplace_dealer_2p", "k_rollout_inplace_dealer_3p", "k_rollout_inplace_dealer_4p"},
-        {"k_rollout_store_dealer_2p", "k_rollout_store_dealer_3p", "k_rollout_store_dealer_4p"}};
-    static const char *const dealer2[2][3] = {
-        {"k_rollout_inplace_dealer2_2p", "k_rollout_inplace_dealer2_3p", "k_rollout_inplace_dealer2_4p"},
-        {"k_rollout_store_dealer2_2p", "k_rollout_store_dealer2_3p", "k_rollout_store_dealer2_4p"}};
-    static const char *const quad[2][3] = {
-        {"k_rollout_inplace_quad_2p", "k_rollout_inplace_quad_3p", "k_rollout_inplace_quad_4p"},
-        {"k_rollout_store_quad_2p", "k_rollout_store_quad_3p", "k_rollout_store_quad_4p"}};
     if (!ctx || n <= 0 || players < 2 || players > 4) {
         fail(SPL_E_ARG, "spl_rollout_kernel_name: bad arguments");
         return nullptr;
     }
-    const int tpw = rollout_tpw(ctx, n, players);
-    if (tpw == 0) return one_wave[players - 2];
-    if (tpw == kDealerShape) return dealer[per_step_outputs ? 1 : 0][players - 2];
-    if (tpw == kDealer2Shape) return dealer2[per_step_outputs ? 1 : 0][players - 2];
-    if (tpw == kQuadShape) return quad[per_step_outputs ? 1 : 0][players - 2];
-    return names[per_step_outputs ? 1 : 0][tpw == 32 ? 1 : 0][players - 2];
+    const int shape = rollout_shape(ctx, n, players);
+    return shape == 0 ? one_wave[players - 2] : rollout_kernel(shape, per_step_outputs != 0, players).name;
 }
 
 int spl_rollout(spl_ctx_t *ctx, spl_arena_t *arena, const spl_step_args_t *a, int32_t steps, int32_t per_step_outputs,
@@ -4644,62 +4352,20 @@ int spl_rollout(spl_ctx_t *ctx, spl_arena_t *arena, const spl_step_args_t *a, in
     const int fused = (due && ctx->refill_fused)
                           ? (int)std::min<int64_t>(steps, (before + steps) / ctx->refill_period - before / ctx->refill_period)
                           : 0;
-    // two-wave kernel (WsLDS<P> fits four workgroups per CU at every player count)
-    // (pipeline 1 = auto, 2 = two-wave at 64 tables per workgroup, 3 = two-wave at 32)
-    const int64_t resident = ctx->ws_resident[arena->players];
-    const int tpw = rollout_tpw(ctx, arena->n, arena->players);
-    const bool p_out = per_step_outputs != 0;
-    // delegation / partner pairs must run at the same time: off when the grid exceeds what is resident
-    // at once.  The two-wave kernel's `deleg`: the static delegation period (>= 4) or 0 (round 5: the
-    // partner hand-off is the six-wave dealer's only)
-    const int deleg = ((int64_t)blocks_for(arena->n) <= resident && ctx->deleg_every > 0) ? ctx->deleg_every : 0;
-    // the six-wave dealer's partner lead, likewise 0 unless every workgroup is resident (ADVICE r04:
-    // pipeline "dealer2" forced on a larger grid)
-    const int lead2 = (int64_t)((arena->n + 127) / 128) <= ctx->dealer2_resident[arena->players] ? ctx->partner_lead : 0;
-    const int lead4 = (int64_t)((arena->n + 255) / 256) <= ctx->quad_resident[arena->players] ? ctx->partner_lead : 0;
-#define SPL_LAUNCH_WS(TPW, BLOCKS)                                                                           \
-    DISPATCH_P(arena->players, if (p_out) {                                                                  \
-        hipLaunchKernelGGL((RolloutKernel<PP, TPW, true>::fn), dim3(BLOCKS), dim3(128), 0, s, A, ktables(ctx), S, \
-                           (int)steps, fused, deleg);                                                        \
-    } else {                                                                                                 \
-        hipLaunchKernelGGL((RolloutKernel<PP, TPW, false>::fn), dim3(BLOCKS), dim3(128), 0, s, A, ktables(ctx), S, \
-                           (int)steps, fused, 0);                                                            \
-    })
-    if (tpw == kQuadShape) {
-        const unsigned blocks = (unsigned)((arena->n + 255) / 256);
-        DISPATCH_P(arena->players, if (p_out) {
-            hipLaunchKernelGGL((RolloutQuadKernel<PP, true>::fn), dim3(blocks), dim3(512), 0, s, A, ktables(ctx), S,
-                               (int)steps, fused, lead4);
-        } else {
-            hipLaunchKernelGGL((RolloutQuadKernel<PP, false>::fn), dim3(blocks), dim3(512), 0, s, A, ktables(ctx), S,
-                               (int)steps, fused, 0);
-        })
-    } else if (tpw == kDealer2Shape) {
-        const unsigned blocks = (unsigned)((arena->n + 127) / 128);
-        DISPATCH_P(arena->players, if (p_out) {
-            hipLaunchKernelGGL((RolloutDealer2Kernel<PP, true>::fn), dim3(blocks), dim3(384), 0, s, A, ktables(ctx), S,
-                               (int)steps, fused, lead2);
-        } else {
-            hipLaunchKernelGGL((RolloutDealer2Kernel<PP, false>::fn), dim3(blocks), dim3(384), 0, s, A, ktables(ctx), S,
-                               (int)steps, fused, 0);
-        })
-    } else if (tpw == kDealerShape) {
-        DISPATCH_P(arena->players, if (p_out) {
-            hipLaunchKernelGGL((RolloutDealerKernel<PP, true>::fn), dim3(blocks_for(arena->n)), dim3(192), 0, s, A,
-                               ktables(ctx), S, (int)steps, fused, 0);
-        } else {
-            hipLaunchKernelGGL((RolloutDealerKernel<PP, false>::fn), dim3(blocks_for(arena->n)), dim3(192), 0, s, A,
-                               ktables(ctx), S, (int)steps, fused, 0);
-        })
-    } else if (tpw == 64) {
-        SPL_LAUNCH_WS(64, blocks_for(arena->n));
-    } else if (tpw == 32) {
-        SPL_LAUNCH_WS(32, (unsigned)((arena->n + 31) / 32));
-    } else {
+    const int shape = rollout_shape(ctx, arena->n, arena->players);
+    if (shape == 0) {
         DISPATCH_P(arena->players, hipLaunchKernelGGL(k_rollout<PP>, dim3(blocks_for(arena->n)), dim3(64), 0, s, A,
                                                       ktables(ctx), S, (int)steps, (int)(per_step_outputs != 0), fused));
+    } else {
+        const RolloutKernel &k = rollout_kernel(shape, per_step_outputs != 0, arena->players);
+        // delegation / partner pairs must run at the same time: off when the grid exceeds what is resident
+        // at once (pipeline "dealer2" forced on a larger grid).  The delegation period is >= 4 or 0.
+        int extra = 0;
+        if (k.extra != kExtraNone && rollout_fits(ctx, shape, arena->n, arena->players))
+            extra = k.extra == kExtraLead ? ctx->partner_lead : ctx->deleg_every;
+        hipLaunchKernelGGL(k.fn, dim3((unsigned)((arena->n + k.tpw - 1) / k.tpw)), dim3(k.threads), 0, s, A, ktables(ctx), S,
+                           (int)steps, fused, extra);
     }
-#undef SPL_LAUNCH_WS
     if (int r = launch_check()) return r;
     arena->steps += steps;
     if (fused) arena->epoch += fused;

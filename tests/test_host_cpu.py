@@ -363,7 +363,7 @@ def test_single_hip_runtime_after_load():
 
 
 def test_fresh_deal_mask_constant():
-    """k_step's autoreset mask is the constant kFreshDealMask (spl_engine.hip): legal_moves of
+    """step_ws's autoreset mask is the constant kFreshDealMask (spl_engine.hip): legal_moves of
     every fresh deal, checked here on the oracle over many deals and player counts."""
     import re
     from oracle.oracle import Oracle

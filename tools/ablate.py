@@ -3,7 +3,7 @@
 each eager launch, 2p tables, device random policy, refill every 16).
 
     python tools/ablate.py [--build-only] [--run] [--rollout] [--tables 16384,65536] [--rounds R] [variant ...]
---rollout times k_rollout launches (16 steps each) instead of k_step.  --rounds R alternates the
+--rollout times rollout launches (16 steps each) instead of spl_step.  --rounds R alternates the
 variants R times (one process per variant and round) so box drift hits every arm alike.
 Only spl_engine.hip is recompiled per variant; the other objects come from csrc/obj (run `make` first).
 Outputs are wrong in ablated builds by design; only timings are meaningful.
@@ -16,11 +16,12 @@ import sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, "splendor-gym_amd", "csrc")
 OUTD = os.path.join(REPO, "splendor-gym_amd", "ablate")
-IO = 1 | 2 | 4 | 8 | 16 | 32  # every compute phase compiled out: loads + stores only
-VARIANTS = {"full": 0, "no_legal_pre": 1, "no_apply": 2, "no_legal_post": 4, "no_final": 8, "no_reset": 16,
-            "no_encode": 32, "no_store": 64, "no_encode_store": 96, "only_io": IO,
-            "only_io_no_mask": IO | 128, "only_io_no_small": IO | 256, "only_io_no_tab": IO | 512,
-            "only_io_no_obs": IO | 1024, "only_obs": IO | 128 | 256 | 512, "only_obs_noload": IO | 128 | 256 | 512 | 2048,
+IO = 1 | 2 | 4 | 8 | 32  # every compute phase compiled out: loads + stores only
+# (bits 16, 64, 512 and 2048 were the removed one-wave step kernel's: unused)
+VARIANTS = {"full": 0, "no_legal_pre": 1, "no_apply": 2, "no_legal_post": 4, "no_final": 8,
+            "no_encode": 32, "only_io": IO,
+            "only_io_no_mask": IO | 128, "only_io_no_small": IO | 256,
+            "only_io_no_obs": IO | 1024,
             "no_noble": 8192, "no_toklim": 4096, "no_obs_store": 1024, "no_compute": 2 | 4 | 32,
             "no_deck_gather": 16384, "no_lut_gather": 32768, "no_gathers": 16384 | 32768, "no_mask_store": 128,
             "no_final_legal_post": 8 | 4}

@@ -1,10 +1,16 @@
 // Where does a pool deal's time go?  Per-lane CPython MT19937 init_by_array (serial chain),
 // the deal's output stream, and the full Fisher-Yates deal with its LDS scratch, each on a
 // full grid (1024 waves, one per SIMD) and on the refill's typical grid (273 waves).
-//   hipcc -O3 -std=c++17 --offload-arch=gfx950 [-DSPL_SCRATCH_STRIDE=112] tools/microbench_deal.hip -o ...
+//   hipcc -O3 -std=c++17 --offload-arch=gfx950 [-DMB_SCRATCH_STRIDE=112] tools/microbench_deal.hip -o ...
 #include "../splendor-gym_amd/csrc/spl_engine.hip"
 
 using namespace spl;
+
+// the deal scratch stride under test, in bytes per lane (default: the engine's)
+#ifndef MB_SCRATCH_STRIDE
+#define MB_SCRATCH_STRIDE kScratchStride
+#endif
+constexpr int kMbStride = MB_SCRATCH_STRIDE;
 
 __global__ __launch_bounds__(64) void k_init_only(uint32_t *out, uint32_t seed0) {
     const uint32_t t = blockIdx.x * 64 + threadIdx.x;
@@ -24,10 +30,10 @@ __global__ __launch_bounds__(64) void k_init_outputs(uint32_t *out, uint32_t see
 }
 
 __global__ __launch_bounds__(64) void k_deal(uint8_t *recs, uint32_t *out, uint32_t seed0) {
-    __shared__ uint8_t scr_all[64 * kScratchStride] __attribute__((aligned(16)));
+    __shared__ uint8_t scr_all[64 * kMbStride] __attribute__((aligned(16)));
     const uint32_t t = blockIdx.x * 64 + threadIdx.x;
     Deal d;
-    const uint32_t f = deal_into(seed0 + t * 2654435761u, 2, recs + (size_t)t * 128, &scr_all[threadIdx.x * kScratchStride], d);
+    const uint32_t f = deal_into(seed0 + t * 2654435761u, 2, recs + (size_t)t * 128, &scr_all[threadIdx.x * kMbStride], d);
     out[t] = d.board[0] ^ d.nob0 ^ f;
 }
 

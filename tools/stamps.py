@@ -1,9 +1,10 @@
-"""Per-phase timeline of k_step from in-kernel s_memrealtime stamps (diagnostic build only).
+"""Per-phase timeline of k_step_ws (spl_step's two-wave kernel) from in-kernel s_memrealtime stamps
+(diagnostic build only).
 
     python tools/stamps.py            # build lib_stamps.so (-DSPL_STAMPS) and run on the GPU
     (STAMP_T: tables, default 65536; --build-only here, --run on the box)
-Lane 0 of every wave stamps 12 phase boundaries (see STAMP(i) in spl_engine.hip); we report, per
-phase, the median and max over waves of the time since the kernel's first stamp (10 ns ticks).
+Lane 0 of every wave stamps its phase boundaries (see STAMP(i) in spl_engine.hip); we report, per
+wave role and phase, the median and max over waves of the time since the kernel's first stamp (10 ns ticks).
 Stamped builds fence the scheduler around each stamp: read the SHARES, not the absolute length.
 """
 import json
@@ -13,9 +14,7 @@ import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.environ.get("STAMP_LIB", os.path.join(REPO, "splendor-gym_amd", "ablate", "lib_stamps.so"))
-NAMES = ["start", "loaded+prefetched", "pre-apply", "applied", "step logic", "final obs", "reset done",
-         "encoded", "barrier", "obs stored", "mask+final stored", "end"]
-# k_step_ws (the default spl_step kernel): stamps per wave, wave 0 = rules, wave 1 = output
+# stamps per wave, wave 0 = rules, wave 1 = output
 WS_RULES = ["start", "past hand-off 0", "rules done", "state to LDS (reset done)", "past hand-off 2 (row halves)", "legal mask",
             "end (mask, small outputs, state stored)", "final rows stored (before 5)", "mask block issued (before 6)"]
 WS_OUT = ["start", "tables staged", "past hand-off 0", "past hand-off 1", "past hand-off 2 (rows encoded)", "final rows done",
@@ -65,17 +64,14 @@ def main():
     runs = json.loads(r.stdout.strip().splitlines()[-1])
     import numpy as np
     a = np.array(runs, dtype=np.int64)  # [run, wave slot, 16]
-    ws = (a[0, :, 0] != 0).sum() > a.shape[1] // 2  # k_step_ws stamps two waves per 64 tables
-    if not ws:
-        a = a[:, : a.shape[1] // 2]
     rows = []
     for run in a:
         t0 = run[run[:, 0] > 0, 0].min()
         rows.append(np.where(run > 0, run - t0, -1))
     a = np.stack(rows).astype(np.float64)
     a = np.where(a >= 0, a * 0.01, np.nan)  # 100 MHz ticks -> microseconds since the kernel's first stamp
-    groups = [("k_step", NAMES, a.reshape(-1, 16))] if not ws else [
-        ("k_step_ws rules wave", WS_RULES, a[:, 0::2].reshape(-1, 16)), ("k_step_ws output wave", WS_OUT, a[:, 1::2].reshape(-1, 16))]
+    groups = [("k_step_ws rules wave", WS_RULES, a[:, 0::2].reshape(-1, 16)),
+              ("k_step_ws output wave", WS_OUT, a[:, 1::2].reshape(-1, 16))]
     for title, names, m in groups:
         print(f"{title}: {'phase':26s} {'median us':>10s} {'p90 us':>8s} {'max us':>8s}   ({len(m)} wave-samples)")
         for i, nm in enumerate(names):
@@ -83,26 +79,26 @@ def main():
             if col.size == 0:
                 continue
             print(f"{i:2d} {nm:26s} {np.median(col):10.2f} {np.percentile(col, 90):8.2f} {col.max():8.2f}")
-    if ws:  # the rules wave's tail by its terminal-row count (slot 9: rows | deferred-mask lanes << 8)
-        raw = np.array(runs, dtype=np.int64)[:, 0::2, 9].reshape(-1)
-        fin, dfr = raw & 255, raw >> 8
-        r = a[:, 0::2]
-        tail = (r[:, :, 7] - r[:, :, 4]).reshape(-1)
-        lm = (r[:, :, 5] - r[:, :, 7]).reshape(-1)
-        end = r[:, :, 6].reshape(-1)
-        for n in range(0, 8):
-            sel = fin == n
-            if sel.sum() == 0:
-                continue
-            print(f"rules waves with {n} terminal rows: {sel.sum():6d}, final rows {np.nanmedian(tail[sel]):.2f} us, "
-                  f"legal mask {np.nanmedian(lm[sel]):.2f} us (deferred lanes {np.median(dfr[sel]):.0f}), "
-                  f"end median {np.nanmedian(end[sel]):.2f} max {np.nanmax(end[sel]):.2f}")
-    if ws:  # per XCC (workgroup i runs on XCC i % 8): the rules wave's hand-off 1 and the output wave's end
-        wg = np.arange(a.shape[1] // 2) % 8
-        for title, idx, ph in (("rules: past hand-off 1", 0, 4), ("output: end", 1, WS_OUT.index("end"))):
-            v = a[:, idx::2, ph]
-            print(f"{title} by XCC median/p99: " + " | ".join(
-                f"{np.nanmedian(v[:, wg == x]):.1f}/{np.nanpercentile(v[:, wg == x], 99):.1f}" for x in range(8)))
+    # the rules wave's tail by its terminal-row count (slot 9: rows | deferred-mask lanes << 8)
+    raw = np.array(runs, dtype=np.int64)[:, 0::2, 9].reshape(-1)
+    fin, dfr = raw & 255, raw >> 8
+    r = a[:, 0::2]
+    tail = (r[:, :, 7] - r[:, :, 4]).reshape(-1)
+    lm = (r[:, :, 5] - r[:, :, 7]).reshape(-1)
+    end = r[:, :, 6].reshape(-1)
+    for n in range(0, 8):
+        sel = fin == n
+        if sel.sum() == 0:
+            continue
+        print(f"rules waves with {n} terminal rows: {sel.sum():6d}, final rows {np.nanmedian(tail[sel]):.2f} us, "
+              f"legal mask {np.nanmedian(lm[sel]):.2f} us (deferred lanes {np.median(dfr[sel]):.0f}), "
+              f"end median {np.nanmedian(end[sel]):.2f} max {np.nanmax(end[sel]):.2f}")
+    # per XCC (workgroup i runs on XCC i % 8): the rules wave's hand-off 1 and the output wave's end
+    wg = np.arange(a.shape[1] // 2) % 8
+    for title, idx, ph in (("rules: past hand-off 1", 0, 4), ("output: end", 1, WS_OUT.index("end"))):
+        v = a[:, idx::2, ph]
+        print(f"{title} by XCC median/p99: " + " | ".join(
+            f"{np.nanmedian(v[:, wg == x]):.1f}/{np.nanpercentile(v[:, wg == x], 99):.1f}" for x in range(8)))
     return 0
 
 
