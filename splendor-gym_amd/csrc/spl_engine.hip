@@ -111,6 +111,12 @@ enum : uint32_t {
     BC_BARRIER = 512  // a wave of a multi-team workgroup made another number of s_barriers than 1 + K
 };
 
+__device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63u); }
+// sub-phase stamp hook of step_rules (diagnostic builds pass a stamping one)
+struct NoStamp {
+    __device__ __forceinline__ void operator()(int) const {}
+};
+
 // Phase stamps for the diagnostic build only (-DSPL_STAMPS, tools/stamps.py): lane 0 of every
 // wave records s_memrealtime (100 MHz) at phase boundaries of step_ws.  Never in the product build.
 #ifdef SPL_STAMPS
@@ -152,14 +158,57 @@ __device__ uint64_t *g_wsend;   // [workgroup][2]: s_memrealtime at the output w
             g_wshwid[((size_t)(sid) * 2 + (wave)) * 2 + 1] = __builtin_amdgcn_s_getreg((31 << 11) | 20); \
         }                                                                                        \
     } while (0)
-#define WSSTAMP(i, k) RSTAMP(i, k)
+// a rules / output wave's stamps of one launch (rules_wave, output_wave): at(i, k) is stamp i of step k
+struct WsStamps {
+    int rst_lo[kWsStamps] = {0}, rst_hi[kWsStamps] = {0};
+    uint64_t clk0 = 0, rt0 = 0;
+    struct Sub {  // step_rules' sub-phase hook
+        WsStamps &st;
+        int k;
+        __device__ __forceinline__ void operator()(int i) const { st.at(i, k); }
+    };
+    __device__ __forceinline__ void at(int i, int k) { RSTAMP(i, k); }
+    __device__ __forceinline__ Sub sub(int k) { return Sub{*this, k}; }
+    __device__ __forceinline__ void start() {
+        clk0 = __builtin_amdgcn_s_memtime();
+        rt0 = __builtin_amdgcn_s_memrealtime();
+    }
+    // the rules wave's clocks from start() to now -> g_wsclk[sid]
+    __device__ __forceinline__ void flush_clocks(int sid) const {
+        const uint64_t clk1 = __builtin_amdgcn_s_memtime(), rt1 = __builtin_amdgcn_s_memrealtime();
+        if (g_wsclk && lane_id() == 0) {
+            g_wsclk[sid * 4 + 0] = clk0;
+            g_wsclk[sid * 4 + 1] = rt0;
+            g_wsclk[sid * 4 + 2] = clk1;
+            g_wsclk[sid * 4 + 3] = rt1;
+        }
+    }
+    // the per-step stamps -> g_wsstamps[sid][wave]
+    __device__ __forceinline__ void flush(int sid, int wave, int K) const {
+        if (g_wsstamps && lane_id() < K)
+            for (int i = 0; i < kWsStamps; ++i)
+                g_wsstamps[(((size_t)sid * 2 + wave) * 64 + lane_id()) * kWsStamps + i] =
+                    ((uint64_t)(uint32_t)rst_hi[i] << 32) | (uint32_t)rst_lo[i];
+    }
+    // now -> g_wsend[sid][i]; `drained`: once this wave's stores have completed
+    __device__ __forceinline__ void end(int sid, int i, bool drained) const {
+        if (!g_wsend) return;
+        if (drained) __builtin_amdgcn_s_waitcnt(0);
+        if (lane_id() == 0) g_wsend[sid * 2 + i] = __builtin_amdgcn_s_memrealtime();
+    }
+};
 #else
 #define WSHWID(sid, wave) \
     do {                  \
     } while (0)
-#define WSSTAMP(i, k) \
-    do {              \
-    } while (0)
+struct WsStamps {
+    __device__ __forceinline__ void at(int, int) {}
+    __device__ __forceinline__ NoStamp sub(int) { return NoStamp(); }
+    __device__ __forceinline__ void start() {}
+    __device__ __forceinline__ void flush_clocks(int) const {}
+    __device__ __forceinline__ void flush(int, int, int) const {}
+    __device__ __forceinline__ void end(int, int, bool) const {}
+};
 #define STAMP(i) \
     do {         \
     } while (0)
@@ -241,8 +290,6 @@ __device__ __forceinline__ uint32_t bget(uint32_t w, int k) { return (w >> (8 * 
 __device__ __forceinline__ uint32_t bset(uint32_t w, int k, uint32_t v) {
     return (w & ~(0xFFu << (8 * k))) | ((v & 0xFFu) << (8 * k));
 }
-__device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63u); }
-
 // Cross-lane LDS hand-off inside ONE wave (every workgroup here is a single wave).
 // __syncthreads() would also emit s_waitcnt vmcnt(0): the wave would stall until its pending
 // global stores drain behind every other wave's observation traffic.  LDS executes one wave's
@@ -774,11 +821,6 @@ __device__ __forceinline__ int get_winner(const uint32_t *sw) { return (int)(sw[
 __device__ __forceinline__ bool is_terminal(const uint32_t *sw) {
     return (sw[SW_MISC] & ST_GAME_OVER) && get_to_play(sw) == 0;
 }
-
-// sub-phase stamp hook of step_rules (diagnostic builds pass a stamping lambda)
-struct NoStamp {
-    __device__ __forceinline__ void operator()(int) const {}
-};
 
 // engine/rules.py:196-287 apply_action on the current player (action known legal)
 template <int P, class Stamp>
@@ -2090,6 +2132,7 @@ struct PtShared {
 template <int P>
 struct __align__(16) WsLDS : Consts {
     static constexpr int kW = SW_COUNT + 4 * P;  // state words per table
+    static constexpr int kWaves = 2;             // rules + output
     PtShared pt;
     static constexpr int kTerm = P == 3 ? 7 : (P == 4 ? 15 : 16);  // terminal states listed per step (3p: 7, room for PtShared)
     static constexpr int kScrStride = P == 2 ? kScratchStride : 100;
@@ -2462,12 +2505,22 @@ static const StepKernel kStepKernels[3 * 3] = {SPL_STEP_KERNELS(X)};
 // so flags from earlier launches, graph replays included, never match.
 struct Deleg {
     bool on, producer;
-    int pair, every;
+    int every;
     uint32_t epoch;
+    uint32_t *fl;      // the pair's flag lines
+    uint8_t *pay;      // the pair's payload slots
+    int pend, pend_k;  // producer: task staged at step pend_k, ready flag not yet set
+    uint32_t staged;   // producer: tasks staged (not stored here)
+    __device__ __forceinline__ uint32_t *ready_flag(int j) const { return fl + (DF_TASKS + 2 * j) * kFlagLine; }
+    __device__ __forceinline__ uint32_t *taken_flag(int j) const { return fl + (DF_TASKS + 2 * j + 1) * kFlagLine; }
+    __device__ __forceinline__ uint8_t *slot(int j) const { return pay + (size_t)j * kDelegPayload; }
 };
 __device__ __forceinline__ bool deleg_step(int k, int K, int every) {
     return every > 0 && k % every == every / 2 - 1 && k + 2 < K && k / every < kDelegTasks;
 }
+// the shortest period that delegates at all; from it on the workgroups take their tables by the identity
+// map (delegation pairs blockIdx b and b + 1 on adjacent XCCs)
+__device__ __forceinline__ bool deleg_period(int every) { return every >= 4; }
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_of(const void *base) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), (short)0, 0x7FFFFFF0, 0x00020000);
 }
@@ -2503,6 +2556,93 @@ __device__ __forceinline__ void unstage_state(const uint8_t *slot, Tab<P> &T) {
 #pragma unroll
     for (int w = 0; w < num_words(P); ++w) set_tab_word(T, w, v[w]);
 }
+// one staged task's rows (delegation or partner hand-off): the staged words -> rows in LDS -> the row
+// block (whole wave, 64 full rows)
+template <int P>
+__device__ __forceinline__ void store_staged_task(const uint8_t *slot, uint8_t *rows_lds, const Consts &C, int32_t *dst) {
+    Tab<P> T;
+    unstage_state(slot, T);
+    encode_row(T, rows_lds, C);
+    wave_lds_sync();
+    store_obs_block<64, true>(rows_lds, 64, dst);
+    wave_lds_sync();  // the block's LDS reads are done before the next task's rows land
+}
+// the output wave opens the launch: both workgroups of a full pair take part (the same test on both
+// sides), each counting its own launches
+__device__ __forceinline__ Deleg deleg_open(const KArena &A, int every) {
+    const size_t pair = blockIdx.x >> 1;
+    Deleg dl{false, false, every, 0u, A.dflags + pair * kDelegFlagWords, A.deleg + pair * kDelegTasks * kDelegPayload,
+             -1, -1, 0u};
+    if (deleg_period(every) && (int)(blockIdx.x | 1u) * 64 + 64 <= A.n) {
+        dl.on = true;
+        dl.producer = (blockIdx.x & 1u) != 0;
+        uint32_t *ep = dl.fl + (dl.producer ? DF_PROD_EPOCH : DF_CONS_EPOCH) * kFlagLine;
+        dl.epoch = __builtin_amdgcn_readfirstlane(flag_load(ep)) + 1u;
+        flag_store(ep, dl.epoch);
+    }
+    return dl;
+}
+// producer, at a delegated step k: the tables' words go to the step's slot; a step with a patched row
+// (`big_moves`; its rows are encoded in `rows_lds`) is stored here and the partner skips the task
+template <int P>
+__device__ __forceinline__ void deleg_stage(Deleg &dl, const Tab<P> &T, int k, bool big_moves, const uint8_t *rows_lds,
+                                            int32_t *dst) {
+    const int j = k / dl.every;
+    if (big_moves) {
+        store_obs_block<64, true>(rows_lds, 64, dst);
+        flag_store(dl.ready_flag(j), dl.epoch << 1 | 1u);
+    } else {
+        stage_state(T, dl.slot(j));
+        dl.staged |= 1u << j;
+        dl.pend = j;
+        dl.pend_k = k;
+    }
+}
+// producer, at the end of every step: the task staged two steps ago turns ready
+__device__ __forceinline__ void deleg_release(Deleg &dl, int k) {
+    if (dl.pend >= 0 && k == dl.pend_k + 2) {
+        // release (guide rule (2)): every sc1 store of the staged words has completed
+        // before the ready flag is stored; by now two steps of block stores sit behind
+        // them, so the wait also drains those
+        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+        flag_store(dl.ready_flag(dl.pend), dl.epoch << 1);
+        dl.pend = -1;
+    }
+}
+// consumer, after its own steps: the partner's staged blocks, each as soon as its ready flag shows
+template <int P>
+__device__ __forceinline__ void deleg_consume(const Deleg &dl, int K, uint8_t *rows_lds, const Consts &C, int32_t *obs,
+                                              int n) {
+    const int64_t pt0 = (int64_t)(blockIdx.x + 1) * 64;
+    const uint64_t limit = 200000;  // 2 ms of s_memrealtime (100 MHz) per task at most
+    for (int k = 0; k < K; ++k) {
+        if (!deleg_step(k, K, dl.every)) continue;
+        const int j = k / dl.every;
+        uint32_t f = 0;
+        const uint64_t t_start = __builtin_amdgcn_s_memrealtime();
+        for (;;) {
+            f = __builtin_amdgcn_readfirstlane(flag_load(dl.ready_flag(j)));
+            if ((f >> 1) == dl.epoch || __builtin_amdgcn_s_memrealtime() - t_start > limit) break;
+            __builtin_amdgcn_s_sleep(8);
+        }
+        if ((f >> 1) != dl.epoch) break;  // not seen in time: the producer stores the rest
+        if (f & 1u) continue;              // the producer stored it
+        flag_store(dl.taken_flag(j), dl.epoch);
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        store_staged_task<P>(dl.slot(j), rows_lds, C, obs + ((size_t)k * (size_t)n + pt0) * kObsDim);
+    }
+}
+// producer, after its steps: every staged block whose taken flag is not visible is stored here
+template <int P>
+__device__ __forceinline__ void deleg_reclaim(const Deleg &dl, uint8_t *rows_lds, const Consts &C, int32_t *obs, int n,
+                                              int t0) {
+    for (int j = 0; j < kDelegTasks; ++j) {
+        if (!((dl.staged >> j) & 1u)) continue;
+        const int k = j * dl.every + dl.every / 2 - 1;
+        if (__builtin_amdgcn_readfirstlane(flag_load(dl.taken_flag(j))) == dl.epoch) continue;
+        store_staged_task<P>(dl.slot(j), rows_lds, C, obs + ((size_t)k * (size_t)n + t0) * kObsDim);
+    }
+}
 
 // ---- the dealer wave (rollout for grids of at most two workgroups per CU) ----------------------
 // A pool refill deal is a ~90 us serial integer chain per wave (MT19937 init, stream, Fisher-Yates).
@@ -2537,6 +2677,7 @@ struct DealerLDS {
 };
 template <int P>
 struct __align__(16) WsDealLDS : WsLDS<P> {
+    static constexpr int kWaves = 3;  // rules + output + dealer
     DealerLDS dl;
 };
 static_assert(sizeof(WsDealLDS<2>) <= 81920 && sizeof(WsDealLDS<3>) <= 81920 && sizeof(WsDealLDS<4>) <= 81920,
@@ -2631,6 +2772,21 @@ __device__ unsigned long long g_partner_stats[2];  // tasks stored by the partne
 __device__ __forceinline__ void pt_post_ready(uint32_t *f, uint32_t target, uint32_t seen) {
     if (lane_id() == 0) (void)__hip_atomic_fetch_add(f, target - seen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// The output wave's hand-off state: tasks posted (pseq) and the one staged but not yet READY (slot pend,
+// step pend_k, pend_seen the slot's flag as the producer saw it, for pt_post_ready), partner tasks seen
+// (cseq).  The flags and the partner's progress come from the poller's LDS snapshots.
+struct PtOut {
+    uint32_t pseq, cseq;
+    int pend, pend_k;
+    uint32_t pend_seen;
+};
+// the task staged last (if any): its words have completed, then READY
+__device__ __forceinline__ void pt_ready_staged(const PartnerLink &pl, PtOut &po) {
+    if (po.pend < 0) return;
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+    pt_post_ready(pl.line(pt_ready_line(po.pend)), pt_flag(pl.e, po.pend_k, kPtReady), po.pend_seen);
+    po.pend = -1;
+}
 // lane 0 moves a task flag READY -> TAKEN (agent scope: performed past the XCC's L2); wave-uniform
 __device__ __forceinline__ bool pt_claim(uint32_t *f, uint32_t ready) {
     uint32_t seen = 0u;
@@ -2640,16 +2796,6 @@ __device__ __forceinline__ bool pt_claim(uint32_t *f, uint32_t ready) {
                                              __HIP_MEMORY_SCOPE_AGENT);
     }
     return (uint32_t)__builtin_amdgcn_readfirstlane(seen) == ready;
-}
-// one task's rows: the staged words -> rows in LDS -> the row block (whole wave, 64 full rows)
-template <int P>
-__device__ __forceinline__ void pt_store_task(const uint8_t *slot, uint8_t *rows_lds, const Consts &C, int32_t *dst) {
-    Tab<P> T;
-    unstage_state(slot, T);
-    encode_row(T, rows_lds, C);
-    wave_lds_sync();
-    store_obs_block<64, true>(rows_lds, 64, dst);
-    wave_lds_sync();  // the block's LDS reads are done before the next task's rows land
 }
 // consumer (the partner team's output wave): `v` = the flag of the partner's slot cseq; if it is READY,
 // claim it and store the task's rows (staged through `rows`); true if the slot held a task.  Which
@@ -2670,7 +2816,7 @@ __device__ __forceinline__ bool pt_serve_v(const PartnerLink &pl, uint32_t &cseq
     if (!pt_claim(f, v)) return true;
     if (acquire) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     const int k = (int)((v >> 2) & 0x3FFFu);
-    pt_store_task<P>(pl.slot(j), rows, C, obs + ((size_t)k * (size_t)n + (size_t)pl.t0p) * kObsDim);
+    store_staged_task<P>(pl.slot(j), rows, C, obs + ((size_t)k * (size_t)n + (size_t)pl.t0p) * kObsDim);
     // the slot's words were read (the encode used them) before it is free again; no vmcnt wait: the
     // rows' stores need not have completed
     __asm__ volatile("" ::: "memory");
@@ -2706,15 +2852,12 @@ __device__ __forceinline__ void pt_drain(const PartnerLink &pl, uint32_t &cseq, 
 // waiting), then every task the partner has not taken is claimed back by the same compare-and-swap
 // and its rows are stored here: each handed-off step's rows are stored once, whatever happened after
 template <int P>
-__device__ __forceinline__ void pt_close(const PartnerLink &pl, int ppend, int ppend_k, uint32_t ppend_seen, uint32_t pseq,
-                                         uint8_t *rows, const Consts &C, int32_t *obs, int n, int t0) {
-    if (ppend >= 0) {
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the staged words have completed
-        pt_post_ready(pl.line(pt_ready_line(ppend)), pt_flag(pl.e, ppend_k, kPtReady), ppend_seen);
-    }
+__device__ __forceinline__ void pt_close(const PartnerLink &pl, PtOut &po, uint8_t *rows, const Consts &C, int32_t *obs,
+                                         int n, int t0) {
+    pt_ready_staged(pl, po);
     __builtin_amdgcn_s_waitcnt(0x0F70);  // every READY flag has completed before DONE
     flag_store(pl.line(pt_done_line(pl.side)), pl.e);
-    if (pseq == 0u) return;
+    if (po.pseq == 0u) return;
     uint32_t mine = 0u;  // lane j: slot j's flag (relaxed agent load: global_load sc1)
     if (lane_id() < kPartnerSlots)
         mine = __hip_atomic_load(pl.line(pt_ready_line(pl.side * kPartnerSlots + lane_id())), __ATOMIC_RELAXED,
@@ -2726,31 +2869,44 @@ __device__ __forceinline__ void pt_close(const PartnerLink &pl, int ppend, int p
         uint32_t *f = pl.line(pt_ready_line(pl.side * kPartnerSlots + j));
         if (!pt_claim(f, vj)) continue;
         const int kk = (int)((vj >> 2) & 0x3FFFu);
-        pt_store_task<P>(pl.slot(pl.side * kPartnerSlots + j), rows, C, obs + ((size_t)kk * (size_t)n + (size_t)t0) * kObsDim);
+        store_staged_task<P>(pl.slot(pl.side * kPartnerSlots + j), rows, C, obs + ((size_t)kk * (size_t)n + (size_t)t0) * kObsDim);
         if (lane_id() == 0) atomicAdd(&g_partner_stats[1], 1ull);
     }
 }
 
-// The dealer wave: batches until the rules wave stops and none is left.  An idle wait that runs out
-// ends the dealer quietly: a batch posted after that is never dealt, so the rules wave's wait for it
-// runs out and faults the launch (lds_wait_ge).  A faulted workgroup's dealer ends after its batch.
-// the dealer wave's poll of the pair's words for its output wave (a snapshot; tags say which slots)
-__device__ __forceinline__ void pt_publish(PtShared &X, uint32_t a, uint32_t b, uint32_t ps, uint32_t c, uint32_t cs,
-                                           int qpar = -1) {
+// The poll of the pair's words for the output wave (a snapshot; tags say which slots), by the dealer
+// wave between batches or by the quad kernel's rules wave.
+// what a poller loads for its output wave: the partner's progress, this side's next slot's flag (slot
+// of task ps) and the partner's next slot's flag (slot of task cs); the loads are not waited for here
+struct PtPolled {
+    uint32_t a, b, c, ps, cs;
+};
+__device__ __forceinline__ PtPolled pt_load(PtShared &X, const PartnerLink &pl) {
+    PtPolled q;
+    q.ps = lds_poll(&X.seq[0]);
+    q.cs = lds_poll(&X.seq[1]);
+    q.a = flag_load(pl.line(pt_progress_line(pl.side ^ 1)));
+    q.b = flag_load(pl.line(pt_ready_line(pl.side * kPartnerSlots + (int)(q.ps % kPartnerSlots))));
+    q.c = flag_load(pl.line(pt_ready_line((pl.side ^ 1) * kPartnerSlots + (int)(q.cs % kPartnerSlots))));
+    return q;
+}
+// qpar >= 0: the consumer's entry by the polling step's parity (PtShared::qcons)
+__device__ __forceinline__ void pt_publish(PtShared &X, const PtPolled &q, int qpar = -1) {
+    const uint32_t a = (uint32_t)__builtin_amdgcn_readfirstlane(q.a), b = (uint32_t)__builtin_amdgcn_readfirstlane(q.b),
+                   c = (uint32_t)__builtin_amdgcn_readfirstlane(q.c);
     if (lane_id() == 0) {
         __hip_atomic_store(&X.in[0], (uint64_t)a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_store(&X.in[1], (uint64_t)ps << 32 | b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_store(qpar < 0 ? &X.in[2] : &X.qcons[qpar], (uint64_t)cs << 32 | c, __ATOMIC_RELAXED,
+        __hip_atomic_store(&X.in[1], (uint64_t)q.ps << 32 | b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_store(qpar < 0 ? &X.in[2] : &X.qcons[qpar], (uint64_t)q.cs << 32 | c, __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_WORKGROUP);
     }
 }
-__device__ __forceinline__ void pt_poll(PtShared &X, const PartnerLink &pl) {
-    const uint32_t ps = lds_poll(&X.seq[0]), cs = lds_poll(&X.seq[1]);
-    const uint32_t a = flag_load(pl.line(pt_progress_line(pl.side ^ 1)));
-    const uint32_t b = flag_load(pl.line(pt_ready_line(pl.side * kPartnerSlots + (int)(ps % kPartnerSlots))));
-    const uint32_t c = flag_load(pl.line(pt_ready_line((pl.side ^ 1) * kPartnerSlots + (int)(cs % kPartnerSlots))));
-    pt_publish(X, (uint32_t)__builtin_amdgcn_readfirstlane(a), (uint32_t)__builtin_amdgcn_readfirstlane(b), ps,
-               (uint32_t)__builtin_amdgcn_readfirstlane(c), cs);
+__device__ __forceinline__ void pt_poll(PtShared &X, const PartnerLink &pl) { pt_publish(X, pt_load(X, pl)); }
+// the quad kernel's poller, once per step of its rules wave (which issues no row stores): the words
+// loaded last step go to the output wave's snapshots, then new loads
+__device__ __forceinline__ void pt_poll_ahead(PtShared &X, const PartnerLink &pl, PtPolled &q, int k) {
+    if (k > 0) pt_publish(X, q, k & 1);
+    q = pt_load(X, pl);
 }
 __device__ __forceinline__ uint64_t lds_poll64(const uint64_t *p) {
     const uint64_t v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -2758,7 +2914,43 @@ __device__ __forceinline__ uint64_t lds_poll64(const uint64_t *p) {
     return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)v) |
            (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32;
 }
+// the output wave at the top of step k: the task staged last step turns READY, then at most one of the
+// partner's tasks, between this team's steps (the poller's snapshot of its next slot, if it is for the
+// task this wave expects).  The quad kernel reads the snapshot its rules wave published at step k - 1,
+// before the s_barrier of step k - 1 that this wave has passed (PtShared::qcons); the six-wave dealer
+// acquires instead.
+template <int P, bool kDealer>
+__device__ __forceinline__ void pt_step_top(const PartnerLink &pl, PtOut &po, PtShared &X, int k, uint8_t *rows,
+                                            const Consts &C, int32_t *obs, int n) {
+    pt_ready_staged(pl, po);
+    const uint64_t nx = kDealer ? lds_poll64(&X.in[2]) : lds_poll64(&X.qcons[(k + 1) & 1]);
+    if ((uint32_t)(nx >> 32) == po.cseq && pt_serve_v<P>(pl, po.cseq, (uint32_t)nx, rows, C, obs, n, kDealer) &&
+        lane_id() == 0)
+        __hip_atomic_store(&X.seq[1], po.cseq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+// the output wave with step k's state: hand the step's rows to the partner if it is `lead` steps ahead and
+// the next slot is free (or stale), by a snapshot taken for this very slot.  True: the words are staged
+// (READY follows at the top of the next step, or in pt_close) and this wave skips the encode and the rows.
+template <int P>
+__device__ __forceinline__ bool pt_hand_off(const PartnerLink &pl, PtOut &po, PtShared &X, const Tab<P> &T, int k) {
+    const uint32_t pp = (uint32_t)lds_poll64(&X.in[0]);
+    const uint64_t ms = lds_poll64(&X.in[1]);
+    const uint32_t sf = (uint32_t)ms;
+    const bool ahead = pl.lead < 0 || ((pp >> 16) == pl.e && (int)(pp & 0xFFFFu) >= k + pl.lead);
+    if (!(ahead && (uint32_t)(ms >> 32) == po.pseq && ((sf & 3u) == 0u || (sf >> 16) != pl.e))) return false;
+    const int j = pl.side * kPartnerSlots + (int)(po.pseq % kPartnerSlots);
+    stage_state(T, pl.slot(j));
+    po.pend = j;
+    po.pend_k = k;
+    po.pend_seen = (uint32_t)__builtin_amdgcn_readfirstlane(sf);
+    ++po.pseq;
+    if (lane_id() == 0) __hip_atomic_store(&X.seq[0], po.pseq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    return true;
+}
 
+// The dealer wave: batches until the rules wave stops and none is left.  An idle wait that runs out
+// ends the dealer quietly: a batch posted after that is never dealt, so the rules wave's wait for it
+// runs out and faults the launch (lds_wait_ge).  A faulted workgroup's dealer ends after its batch.
 template <int P>
 __device__ __forceinline__ void dealer_loop(DealerLDS &D, const KArena &A, int t0, const PartnerLink &pl, PtShared &X) {
     const int lane = lane_id();
@@ -2880,56 +3072,346 @@ __device__ __forceinline__ bool dealer_step(DealerLDS &D, Tab<P> &T, const KAren
 // kStore: per-step outputs (a [K][n][...] rollout store) or every step into the same [n][...] block;
 // a template argument so that the two variants are separate kernels in a profile.
 // kDealer: a third wave deals the pool refills (DealerLDS above; 64 tables per workgroup).
-// A wave's role in rollout_ws (0 rules, 1 output, 2 dealer) and the block of TPW tables it serves;
-// the default (role -1) takes both from the thread index and the workgroup (one block per workgroup).
+// kTeams: 64-table teams per workgroup (the six-wave dealer 2, the quad kernel 4; one workgroup per CU)
+// Which of the two cross-XCC hand-offs a shape can use follows from these; the code of each is compiled
+// into those kernels only.
+template <int P_, int TPW_, bool kStore_, bool kDealer_, int kTeams_>
+struct WsShape {
+    static_assert(TPW_ == 64 || TPW_ == 32, "64 or 32 tables per workgroup");
+    static_assert(!kDealer_ || TPW_ == 64, "the dealer variant runs 64 tables per workgroup");
+    static constexpr int P = P_, TPW = TPW_, kTeams = kTeams_;
+    static constexpr bool kStore = kStore_, kDealer = kDealer_;
+    // rollout-store delegation (Deleg): the full two-wave store kernel
+    static constexpr bool kDeleg = TPW == 64 && kStore && !kDealer && kTeams == 1;
+    // partner hand-off (PartnerLink; per-step outputs, 64 tables per team): the multi-team kernels only —
+    // one workgroup per CU, the guide's first measured row (the six-wave dealer and, round 5, the quad
+    // kernel; not the two-wave kernel at four workgroups per CU)
+    static constexpr bool kPartner = kStore && kTeams > 1;
+};
+// A wave's role in rollout_ws (0 rules, 1 output, 2 dealer) and the block of TPW tables it serves, as a
+// multi-team kernel assigns them (team_assign); a one-team kernel takes both from the thread index and
+// the workgroup (one block per workgroup).
 struct WaveRole {
     int role, block;
 };
-// kTeams: 64-table teams per workgroup (the six-wave dealer 2, the quad kernel 4; one workgroup per CU)
+// What a wave of rollout_ws knows about itself, settled once before the roles split.
+struct WsWave {
+    int lane, role;   // role: 0 rules, 1 output, 2 dealer
+    int t0, t;        // the team's first table, this lane's table
+    bool valid;       // the lane has a table
+    int rows;         // the team's tables (TPW, fewer in the grid's last block)
+    int sid;          // the team's number in the grid (its 64-table block in a multi-team kernel, else the
+                      // workgroup): stamp slot of the diagnostic builds, stagger of the fused refills
+    bool want_final;  // terminal rows are wanted (info["final_observation"])
+    bool multi;       // a multi-team kernel: role and block came with a WaveRole
+};
+
+// The rules wave lists its terminal states of a step, before the autoreset replaces them, for the output
+// wave: the first kTerm in L.tst[b], in lane order; any further row it stores itself (`row`: the table's
+// row index in final_obs).  Returns the lanes listed (L.fin[b], once the step is handed off).
+template <int P, class LdsT>
+__device__ __forceinline__ uint64_t list_terminal(const Tab<P> &T, LdsT &L, int b, bool fin_me, int32_t *final_obs,
+                                                  size_t row) {
+    const int idx = __popcll(__ballot(fin_me) & ((1ull << lane_id()) - 1ull));
+    if (fin_me) {
+        if (idx < WsLDS<P>::kTerm) {
+#pragma unroll
+            for (int w = 0; w < WsLDS<P>::kW; ++w) L.tst[b][idx][w] = tab_word(T, w);
+        } else {
+            store_row_direct(T, L, final_obs + row * kObsDim);
+        }
+    }
+    return __ballot(fin_me && idx < WsLDS<P>::kTerm);
+}
+// The output wave stores a lane's small outputs of a step as the rules wave packed them (pack_small),
+// at index i = blk + t, and the episode statistics of table t.
+__device__ __forceinline__ void store_small(uint32_t sm, const KStep &S, size_t i, int t) {
+    if (!(sm & (1u << 9))) return;  // no table in this lane
+    if (!abl(ABL_SMALL_OUT)) {
+        S.reward[i] = reward_of_code((sm >> 13) & 7u);
+        S.terminated[i] = (uint8_t)((sm >> 8) & 1u);
+        S.flags[i] = (uint8_t)(sm & 0xFFu);
+        if (S.winner) S.winner[i] = (int8_t)((int)((sm >> 10) & 7u) - 1);
+    }
+    if (sm & (1u << 18)) {  // same per-table order and float rounding as step_ws
+        if (S.ep_return) unsafeAtomicAdd(&S.ep_return[t], ep_of_code((sm >> 16) & 3u));
+        if (S.ep_count) atomicAdd(&S.ep_count[t], 1u);
+    }
+}
+// A faulted workgroup's steps k.. are not stored: their flags say so (the blocks keep stale rows)
+template <bool per_step>
+__device__ __forceinline__ void mark_unstored(const KStep &S, int k, int K, int n, int t, bool valid) {
+    for (int j = per_step ? k : 0; j < K && (per_step || j == 0); ++j)
+        if (valid) S.flags[(per_step ? (size_t)j * (size_t)n : 0) + t] = (uint8_t)SPL_F_FAULT;
+}
+
+// The rules wave of a team: K steps of its tables, each handed to the output wave in buffers k & 1.
 // Barrier invariant: without a dealer wave the two waves of a team hand off through
 // ws_sync(), an s_barrier of the WHOLE workgroup — in the quad kernel (kTeams = 4) all eight waves pass
 // each barrier together.  That is correct only because every wave makes exactly 1 + K ws_sync() calls
-// (one before the roles split, one per step) and none returns early: a per-team early exit or an extra
-// barrier would deadlock the workgroup or pair different steps.  Only the dealer variants leave early
-// (their fault path), and they hand off through LDS counters, not barriers.  The bounds-check build
-// counts each wave's barriers and flags BC_BARRIER when a wave ends with another count.
-template <int P, int TPW, bool kStore, bool kDealer = false, class LdsT = WsLDS<P>, int kTeams = 1>
-__device__ __forceinline__ void rollout_ws(LdsT &L, KArena A, KTables Tb, KStep S, int K, int refill,
-                                           int deleg_every, WaveRole wr = WaveRole{-1, -1}) {
-    static_assert(TPW == 64 || TPW == 32, "64 or 32 tables per workgroup");
-    static_assert(!kDealer || TPW == 64, "the dealer variant runs 64 tables per workgroup");
-    constexpr bool per_step = kStore;
+// (one in rollout_ws before the roles split, one per step of the loop below and of output_wave's) and
+// none returns early: a per-team early exit or an extra barrier would deadlock the workgroup or pair
+// different steps.  Only the dealer variants leave early (their fault path), and they hand off through
+// LDS counters, not barriers.  The bounds-check build counts each wave's barriers and flags BC_BARRIER
+// when a wave ends with another count.
+template <class Sh, class LdsT>
+__device__ __forceinline__ void rules_wave(LdsT &L, const KArena &A, const KTables &Tb, const KStep &S, int K, int refill,
+                                           const WsWave &w, const PartnerLink &pl) {
+    constexpr int P = Sh::P;
+    constexpr bool per_step = Sh::kStore, kDealer = Sh::kDealer;
     constexpr int kW = WsLDS<P>::kW;
-    const int lane = lane_id();
-    const int role = wr.role >= 0 ? wr.role : (int)(threadIdx.x >> 6);
-    const bool rules_wave = role == 0;
+    const int lane = w.lane, t = w.t;
+    const bool valid = w.valid;
+    WsStamps st;
+    st.start();
+    const RefillSlots rs = refill_slots(K, (S.autoreset && !kDealer) ? refill : 0, (uint32_t)w.sid);
+    // dealer bookkeeping (per lane): slots whose deal is in flight (valid while a batch is
+    // outstanding) and whether `pool` still lacks the next record's words
+    uint32_t my_req = 0, infl = 0;
+    bool pool_stale = false;
+    bool faulted = false;  // a dealer hand-off ran out (wave-uniform): stop, store nothing more
+    Tab<P> T;
+    int action = 0;
+    Deal pool = empty_deal();
+    if (valid) {
+        load_tab(T, A, t);
+        action = S.actions[t];
+        if (S.autoreset) pool = load_pool(A, t);
+    } else {
+        fresh_state(T, 0u, empty_deal());
+    }
+    StepPre pre = step_prefetch(T, action, valid, A, t, Tb);
+    bool pool_dirty = false;
+    const uint64_t ply0 = S.ply + (S.ply_base ? *S.ply_base : 0ull);
+    uint64_t cur_mask = 0ull;
+    PtPolled polled{0u, 0u, 0u, 0u, 0u};  // quad kernel's partner poller (loaded a step ahead)
+    int nsync = 0;  // ws_sync() calls in the steps (the barrier invariant above)
+    for (int k = 0; k < K; ++k) {
+        const int b = k & 1;
+        const size_t blk = per_step ? (size_t)k * (size_t)A.n : 0;
+        st.at(0, k);
+        if constexpr (kDealer) {
+            if (k >= 2 && !lds_wait_ge(L.dl, &L.dl.odone, (uint32_t)(k - 1))) {  // slot b: step k-2 is stored
+                faulted = true;
+                break;
+            }
+        }
+        // token-return continuation (LaneMT) in this step's free state slot
+        StepOut o = step_rules(T, action, pre, valid, L, Tb, &L.st[b][0][0], k > 0, cur_mask, false, st.sub(k));
+        st.at(1, k);
+        if (rs.due(k) && valid && pend_of(T.sw[SW_MISC]) > 0)  // fused pool refill
+            T.sw[SW_MISC] = refill_table<P>(A, t, T.sw[SW_MISC], L.scratch(b, lane), L.deal_mtx(b), pool, pool_dirty);
+        const int8_t wnr = (int8_t)get_winner(T.sw);
+        const uint64_t fin_listed = list_terminal(T, L, b, valid && o.term && w.want_final, S.final_obs, blk + (size_t)t);
+        const float ep_add = (valid && o.term) ? final_reward_p0(T) : 0.0f;  // per termination, as step_ws
+        if constexpr (kDealer) {
+            if (!dealer_step<P>(L.dl, T, A, t, valid, valid && o.term && S.autoreset, S.autoreset != 0, pool,
+                                pool_dirty, my_req, infl, pool_stale, o)) {
+                faulted = true;
+                break;
+            }
+        } else {
+            if (valid && o.term && S.autoreset)
+                autoreset_table(T, A, t, pool, L.scratch(b, lane), L.deal_mtx(b), o, pool_dirty);
+        }
+        st.at(7, k);
+        L.small[b][lane] = pack_small(valid, o, wnr, valid && o.term, ep_add);  // stored by the output wave
+        if (kDealer && S.policy == SPL_POLICY_UNIFORM && k >= 2) {
+            // the Philox word was drawn by the output wave at step k - 2 (it published odone >= k - 1
+            // after writing it, which this step waited for): only the scaling stays on this chain
+            if constexpr (kDealer) action = sample_uniform_word(o.mask, L.dl.rnd[b][lane]);
+        } else {
+            action = policy_action(S.policy, o.mask, T, L, S.policy_seed, (uint64_t)(S.table0 + t), ply0 + (uint64_t)k);
+        }
+        cur_mask = o.mask;
+        if (k + 1 < K) pre = step_prefetch(T, action, valid, A, t, Tb);
+#pragma unroll
+        for (int i = 0; i < kW; ++i) L.st[b][i][lane] = tab_word(T, i);
+        L.mask[b][lane] = o.mask;
+        if (lane == 0) L.fin[b] = fin_listed;
+        st.at(2, k);
+        if constexpr (kDealer) {
+            lds_publish(&L.dl.rdone, (uint32_t)(k + 1));  // hand-off of step k
+        } else {
+            if constexpr (Sh::kPartner) {
+                if (pl.on) pt_poll_ahead(L.pt, pl, polled, k);
+            }
+            ws_sync();  // hand-off of step k
+            ++nsync;
+        }
+        st.at(3, k);
+    }
+    if constexpr (kDealer) {  // no more batches; the last one lands before the state is stored
+        lds_publish(&L.dl.stop, 1u);
+        if (!faulted && !lds_wait_ge(L.dl, &L.dl.ddone, my_req)) faulted = true;
+        if (pool_stale && !faulted) {
+            pool = deal_of_lds(L.dl, lane);
+            pool_dirty = true;
+        }
+        if (faulted) {  // the tables' state is not stored: the host sees the fault and resets
+            signal_fault(S);
+            return;
+        }
+    }
+    st.flush_clocks(w.sid);
+    st.flush(w.sid, 0, K);
+    SPL_CHECK(kDealer || nsync == K, BC_BARRIER);
+    (void)nsync;
+    if (valid) {
+        if (S.next_actions) S.next_actions[t] = action;
+        store_tab(T, A, t, cur_mask, K > 0 ? Tb.mtag : 0u);  // cur_mask: the last step's mask of this state
+        if (pool_dirty) store_pool(A, t, pool);
+    }
+}
+
+// The output wave of a team: every global write of a step (why: the comment at pack_small), from the
+// buffers the rules wave handed off.  `extra`: the delegation period (read by the Sh::kDeleg kernels only).
+template <class Sh, class LdsT>
+__device__ __forceinline__ void output_wave(LdsT &L, const KArena &A, const KStep &S, int K, int extra, const WsWave &w,
+                                            const PartnerLink &pl) {
+    constexpr int P = Sh::P, TPW = Sh::TPW;
+    constexpr bool per_step = Sh::kStore, kDealer = Sh::kDealer, kDeleg = Sh::kDeleg, kPartner = Sh::kPartner;
+    constexpr int kW = WsLDS<P>::kW;
+    const int lane = w.lane, t = w.t, t0 = w.t0;
+    const bool valid = w.valid;
+    const ColRecipes crc = col_recipes();  // this lane's bytes of a column-parallel terminal row
+    const uint64_t ply0 = S.ply + (S.ply_base ? *S.ply_base : 0ull);  // the policy words drawn ahead (dealer)
+    (void)ply0;
+    WsStamps st;
+    Deleg dl{};
+    if constexpr (kDeleg) dl = deleg_open(A, extra);
+    PtOut po{0u, 0u, -1, 0, 0u};
+    int osync = 0;  // ws_sync() calls in the steps (the barrier invariant at rules_wave)
+    for (int k = 0; k < K; ++k) {
+        if constexpr (kPartner) {
+            if (pl.on) pt_step_top<P, kDealer>(pl, po, L.pt, k, L.rows, L, S.obs, A.n);
+        }
+        if constexpr (kDealer) {
+            if (!lds_wait_ge(L.dl, &L.dl.rdone, (uint32_t)(k + 1))) {  // hand-off of step k
+                mark_unstored<per_step>(S, k, K, A.n, t, valid);
+                // steps before k that were handed to the partner: DONE, and those it has not taken are
+                // stored here (they were stepped before the fault)
+                if constexpr (kPartner) {
+                    if (pl.on) pt_close<P>(pl, po, L.rows, L, S.obs, A.n, t0);
+                }
+                signal_fault(S);
+                return;
+            }
+        } else {
+            ws_sync();  // hand-off of step k
+            ++osync;
+        }
+        st.at(0, k);
+        const int b = k & 1;
+        const size_t blk = per_step ? (size_t)k * (size_t)A.n : 0;
+        Tab<P> T;
+#pragma unroll
+        for (int i = 0; i < kW; ++i) set_tab_word(T, i, L.st[b][i][lane]);
+        // terminal rows (info["final_observation"]) first: each by the whole wave, column-parallel,
+        // straight from its listed state words (no staging, no LDS barrier)
+        // (readfirstlane returns int: widen through uint32_t, or bit 31 sign-extends into lanes 32-63)
+        uint64_t fin = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)L.fin[b]) |
+                       ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(L.fin[b] >> 32)) << 32);
+        if (fin) {
+            int32_t *fobs = S.final_obs + blk * kObsDim;
+            for (int idx = 0; fin; fin &= fin - 1, ++idx) {
+                const int r = __ffsll((unsigned long long)fin) - 1;
+                store_row_columns<P>(&L.tst[b][idx][0], 1, L, crc, fobs + (size_t)(t0 + r) * kObsDim);
+            }
+        }
+        const bool big_moves = __any(valid && get_moves(T.sw) > 255);
+        bool deleg_now = false;  // a delegated step: the rows are encoded by the partner workgroup
+        if constexpr (kDeleg) deleg_now = dl.producer && deleg_step(k, K, dl.every);
+        bool handed = false;  // partner hand-off of this step's rows
+        if constexpr (kPartner) {
+            if (pl.on && !big_moves) handed = pt_hand_off(pl, po, L.pt, T, k);
+        }
+        if (!handed && (!deleg_now || big_moves)) {
+            encode_row(T, L.rows, L);
+            wave_lds_sync();
+        }
+        st.at(1, k);
+        int32_t *obs = S.obs + blk * kObsDim;
+        if (handed) {
+        } else if (deleg_now) {
+            if constexpr (kDeleg) deleg_stage(dl, T, k, big_moves, L.rows, obs + (size_t)t0 * kObsDim);
+        } else if (abl(ABL_OBS_STORE)) {
+        } else {  // per-step blocks through the NT stream, in-place ones plain (kRollCpol's comment)
+            store_obs_block<TPW, per_step>(L.rows, w.rows, obs + (size_t)t0 * kObsDim);
+        }
+        st.at(2, k);
+        if (!abl(ABL_MASK_STORE)) store_mask_block<per_step>(L.mask[b], L.mbits, w.rows, S.mask + blk * 45 + (size_t)t0 * 45);
+        store_small(L.small[b][lane], S, blk + t, t);
+        if (big_moves) {
+            __builtin_amdgcn_s_waitcnt(0);
+            if (valid && get_moves(T.sw) > 255) obs[(size_t)t * kObsDim + 295] = get_moves(T.sw);
+        }
+        if constexpr (kDeleg) deleg_release(dl, k);
+        if constexpr (kDealer) {
+            if (S.policy == SPL_POLICY_UNIFORM && k + 2 < K)  // step k + 2's policy word, slot b again
+                L.dl.rnd[b][lane] = uniform_draw(S.policy_seed, (uint64_t)(S.table0 + t), ply0 + (uint64_t)(k + 2));
+            lds_publish(&L.dl.odone, (uint32_t)(k + 1));  // slot b is free again
+        }
+        if constexpr (kPartner) {
+            if (pl.on)  // this side's progress, for the partner's decisions (a write-through store, no wait)
+                flag_store(pl.line(pt_progress_line(pl.side)), pl.e << 16 | (uint32_t)(k + 1));
+        }
+        st.at(3, k);
+    }
+    SPL_CHECK(kDealer || osync == K, BC_BARRIER);
+    (void)osync;
+    if constexpr (kPartner) {
+        if (pl.on) {
+            pt_close<P>(pl, po, L.rows, L, S.obs, A.n, t0);
+            pt_drain<P>(pl, po.cseq, L.rows, L, S.obs, A.n);  // then the partner's, until it is done
+        }
+    }
+    st.end(w.sid, 0, false);
+    if constexpr (kDeleg) {
+        if (dl.on && !dl.producer) deleg_consume<P>(dl, K, L.rows, L, S.obs, A.n);
+        if (dl.producer && dl.staged) deleg_reclaim<P>(dl, L.rows, L, S.obs, A.n, t0);
+    }
+    st.end(w.sid, 1, true);
+    st.flush(w.sid, 1, K);
+}
+
+// A team of the multi-wave rollout: the set-up all its waves share, the first ws_sync(), then each wave
+// to its role (rules_wave, output_wave, dealer_loop).
+// `extra` is the kernel's last argument, whose meaning the kernel's RolloutExtra names: the delegation
+// period (kExtraDeleg, the Sh::kDeleg kernels), the partner lead in steps (kExtraLead, the Sh::kPartner
+// kernels; 0 = off, -1 = forced), or nothing (kExtraNone).
+template <int P, int TPW, bool kStore, bool kDealer = false, class LdsT = WsLDS<P>, int kTeams = 1>
+__device__ __forceinline__ void rollout_ws(LdsT &L, KArena A, KTables Tb, KStep S, int K, int refill, int extra,
+                                           WaveRole wr = WaveRole{-1, -1}) {
+    using Sh = WsShape<P, TPW, kStore, kDealer, kTeams>;
+    WsWave w;
+    w.lane = lane_id();
+    w.multi = kTeams > 1;
+    w.role = w.multi ? wr.role : (int)(threadIdx.x >> 6);
     // delegation pairs neighbouring workgroups (blockIdx b and b + 1 on adjacent XCCs): identity map
-    const bool deleg_shape = TPW == 64 && kStore && !kDealer && kTeams == 1 && deleg_every >= 4;
-    const int t0 = (wr.block >= 0 ? wr.block : (deleg_shape ? (int)blockIdx.x : wg_block())) * TPW;
-    const int t = t0 + lane;
-    const bool valid = lane < TPW && t < A.n;
-    const int rows = min(TPW, A.n - t0);
-    const bool want_final = S.autoreset && S.final_obs != nullptr;
+    const bool deleg_ids = Sh::kDeleg && deleg_period(extra);
+    w.t0 = (w.multi ? wr.block : (deleg_ids ? (int)blockIdx.x : wg_block())) * TPW;
+    w.t = w.t0 + w.lane;
+    w.valid = w.lane < TPW && w.t < A.n;
+    w.rows = min(TPW, A.n - w.t0);
+    w.sid = w.multi ? wr.block : (int)blockIdx.x;
+    w.want_final = S.autoreset && S.final_obs != nullptr;
     load_tables_lds(L, Tb);
     if constexpr (kDealer) {  // the hand-off counters start at zero (LDS is not initialised)
-        if (rules_wave && lane == 0) {
+        if (w.role == 0 && w.lane == 0) {
             L.dl.dreq = L.dl.ddone = L.dl.rdone = L.dl.odone = L.dl.stop = L.dl.abort = 0u;
         }
     }
-    // partner hand-off (per-step outputs, 64 tables per team; see PartnerLink): the multi-team kernels
-    // only — one workgroup per CU, the guide's first measured row (the six-wave dealer and, round 5, the
-    // quad kernel; not the two-wave kernel at four workgroups per CU), which pass the lead in steps as
-    // deleg_every (0 = off, -1 = forced).  Team j of workgroups b and b ^ 1, both full, K < 2^14 (the
-    // step fits a flag).
+    // partner link: team j of workgroups b and b ^ 1, both full, K < 2^14 (the step fits a flag)
     PartnerLink pl{false, 0, 0, 0u, nullptr, nullptr, 0};
-    if constexpr (kStore && kTeams > 1) {
-        const int lead = wr.block >= 0 ? deleg_every : 0;
+    if constexpr (Sh::kPartner) {
+        const int lead = extra;
         if (lead != 0 && K < (1 << 14)) {
             const uint32_t b = blockIdx.x, pb = b ^ 1u;
             const int team = wr.block - kTeams * wg_block();
             const int t0p = (kTeams * wg_block_of(pb) + team) * 64;
             const int pair = (int)(b >> 1) * kTeams + team;
-            if (pb < gridDim.x && t0 + 64 <= A.n && t0p + 64 <= A.n && pair < A.n / 128) {
+            if (pb < gridDim.x && w.t0 + 64 <= A.n && t0p + 64 <= A.n && pair < A.n / 128) {
                 pl.on = true;
                 pl.lead = lead;
                 pl.side = (int)(b & 1u);
@@ -2938,13 +3420,13 @@ __device__ __forceinline__ void rollout_ws(LdsT &L, KArena A, KTables Tb, KStep 
                 pl.pay = A.deleg + (size_t)pair * kDelegTasks * kDelegPayload;
             }
         }
-        if (pl.on && role == 1) {  // this side's launch counter: the output wave counts, the poller reads it
+        if (pl.on && w.role == 1) {  // this side's launch counter: the output wave counts, the poller reads it
             uint32_t *el = pl.line(pt_epoch_line(pl.side));
             uint32_t e = ((uint32_t)__builtin_amdgcn_readfirstlane(flag_load(el)) + 1u) & 0xFFFFu;
             e = e == 0u ? 1u : e;
             flag_store(el, e);
             pl.e = e;
-            if (lane == 0) {
+            if (w.lane == 0) {
                 L.pt.pepoch = e;
                 L.pt.seq[0] = L.pt.seq[1] = 0u;
                 L.pt.in[0] = 0ull;
@@ -2953,466 +3435,38 @@ __device__ __forceinline__ void rollout_ws(LdsT &L, KArena A, KTables Tb, KStep 
             }
         }
     }
-    ws_sync();
-    if (pl.on && role != 1) pl.e = (uint32_t)__builtin_amdgcn_readfirstlane(L.pt.pepoch);
-
-    // stamp slot of this team (diagnostic builds): its 64-table block for the six-wave dealer, else the workgroup
-    const int sid = wr.block >= 0 ? wr.block : (int)blockIdx.x;
-    (void)sid;
-    WSHWID(sid, rules_wave ? 0 : 1);
+    ws_sync();  // the first of every wave's 1 + K (the barrier invariant at rules_wave)
+    if constexpr (Sh::kPartner) {
+        if (pl.on && w.role != 1) pl.e = (uint32_t)__builtin_amdgcn_readfirstlane(L.pt.pepoch);
+    }
+    WSHWID(w.sid, w.role == 0 ? 0 : 1);
     // the rules wave is the critical path: it wins issue arbitration against the CU's output
     // waves (rollout store 1134 -> 1103 us per launch on one box; 1 and 3 measure the same)
-    if (rules_wave) __builtin_amdgcn_s_setprio(1);
-#ifdef SPL_STAMPS
-    const uint64_t clk0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
-#endif
+    if (w.role == 0) __builtin_amdgcn_s_setprio(1);
     if constexpr (kDealer) {
-        if (role >= 2) {
-            dealer_loop<P>(L.dl, A, t0, pl, L.pt);
+        if (w.role >= 2) {
+            dealer_loop<P>(L.dl, A, w.t0, pl, L.pt);
             return;
         }
     }
-    if (rules_wave) {
-        const RefillSlots rs = refill_slots(K, (S.autoreset && !kDealer) ? refill : 0,
-                                            wr.block >= 0 ? (uint32_t)wr.block : blockIdx.x);
-        // dealer bookkeeping (per lane): slots whose deal is in flight (valid while a batch is
-        // outstanding) and whether `pool` still lacks the next record's words
-        uint32_t my_req = 0, infl = 0;
-        bool pool_stale = false;
-        bool faulted = false;  // a dealer hand-off ran out (wave-uniform): stop, store nothing more
-        Tab<P> T;
-        int action = 0;
-        Deal pool = empty_deal();
-        if (valid) {
-            load_tab(T, A, t);
-            action = S.actions[t];
-            if (S.autoreset) pool = load_pool(A, t);
-        } else {
-            fresh_state(T, 0u, empty_deal());
-        }
-        StepPre pre = step_prefetch(T, action, valid, A, t, Tb);
-        bool pool_dirty = false;
-        const uint64_t ply0 = S.ply + (S.ply_base ? *S.ply_base : 0ull);
-        uint64_t cur_mask = 0ull;
-        uint32_t pv[3] = {0u, 0u, 0u}, pps = 0u, pcs = 0u;  // quad kernel's partner poller (loaded a step ahead)
-        int nsync = 0;  // ws_sync() calls in the steps (the barrier invariant above)
-        const uint64_t below = (1ull << lane) - 1ull;
-#ifdef SPL_STAMPS
-        int rst_lo[kWsStamps] = {0}, rst_hi[kWsStamps] = {0};
-#endif
-        for (int k = 0; k < K; ++k) {
-            const int b = k & 1;
-            const size_t blk = per_step ? (size_t)k * (size_t)A.n : 0;
-            WSSTAMP(0, k);
-            if constexpr (kDealer) {
-                if (k >= 2 && !lds_wait_ge(L.dl, &L.dl.odone, (uint32_t)(k - 1))) {  // slot b: step k-2 is stored
-                    faulted = true;
-                    break;
-                }
-            }
-            // token-return continuation (LaneMT) in this step's free state slot
-#ifdef SPL_STAMPS
-            auto sub = [&](int i) { WSSTAMP(i, k); };
-            StepOut o = step_rules(T, action, pre, valid, L, Tb, &L.st[b][0][0], k > 0, cur_mask, false, sub);
-#else
-            StepOut o = step_rules(T, action, pre, valid, L, Tb, &L.st[b][0][0], k > 0, cur_mask);
-#endif
-            WSSTAMP(1, k);
-            if (rs.due(k) && valid && pend_of(T.sw[SW_MISC]) > 0)  // fused pool refill
-                T.sw[SW_MISC] = refill_table<P>(A, t, T.sw[SW_MISC], L.scratch(b, lane), L.deal_mtx(b), pool, pool_dirty);
-            const int8_t wnr = (int8_t)get_winner(T.sw);
-            const bool fin_me = valid && o.term && want_final;
-            const uint64_t fin_all = __ballot(fin_me);
-            const int idx = __popcll(fin_all & below);
-            if (fin_me) {  // the terminal state, before the autoreset replaces it
-                if (idx < WsLDS<P>::kTerm) {
-#pragma unroll
-                    for (int w = 0; w < kW; ++w) L.tst[b][idx][w] = tab_word(T, w);
-                } else {
-                    store_row_direct(T, L, S.final_obs + (blk + (size_t)t) * kObsDim);
-                }
-            }
-            const float ep_add = (valid && o.term) ? final_reward_p0(T) : 0.0f;  // per termination, as step_ws
-            if constexpr (kDealer) {
-                if (!dealer_step<P>(L.dl, T, A, t, valid, valid && o.term && S.autoreset, S.autoreset != 0, pool,
-                                    pool_dirty, my_req, infl, pool_stale, o)) {
-                    faulted = true;
-                    break;
-                }
-            } else {
-                if (valid && o.term && S.autoreset)
-                    autoreset_table(T, A, t, pool, L.scratch(b, lane), L.deal_mtx(b), o, pool_dirty);
-            }
-            WSSTAMP(7, k);
-            L.small[b][lane] = pack_small(valid, o, wnr, valid && o.term, ep_add);  // stored by the output wave
-            if (kDealer && S.policy == SPL_POLICY_UNIFORM && k >= 2) {
-                // the Philox word was drawn by the output wave at step k - 2 (it published odone >= k - 1
-                // after writing it, which this step waited for): only the scaling stays on this chain
-                if constexpr (kDealer) action = sample_uniform_word(o.mask, L.dl.rnd[b][lane]);
-            } else {
-                action = policy_action(S.policy, o.mask, T, L, S.policy_seed, (uint64_t)(S.table0 + t), ply0 + (uint64_t)k);
-            }
-            cur_mask = o.mask;
-            if (k + 1 < K) pre = step_prefetch(T, action, valid, A, t, Tb);
-#pragma unroll
-            for (int w = 0; w < kW; ++w) L.st[b][w][lane] = tab_word(T, w);
-            L.mask[b][lane] = o.mask;
-            const uint64_t fin_listed = __ballot(fin_me && idx < WsLDS<P>::kTerm);  // outside the lane-0 branch
-            if (lane == 0) L.fin[b] = fin_listed;
-            WSSTAMP(2, k);
-            if constexpr (kDealer) {
-                lds_publish(&L.dl.rdone, (uint32_t)(k + 1));  // hand-off of step k
-            } else {
-                if (pl.on) {  // the quad kernel's partner poller (the rules wave issues no row stores): the
-                              // words loaded last step go to the output wave's snapshots, then new loads
-                    if (k > 0)  // the consumer's entry by this step's parity (PtShared::qcons)
-                        pt_publish(L.pt, (uint32_t)__builtin_amdgcn_readfirstlane(pv[0]),
-                                   (uint32_t)__builtin_amdgcn_readfirstlane(pv[1]), pps,
-                                   (uint32_t)__builtin_amdgcn_readfirstlane(pv[2]), pcs, k & 1);
-                    pps = lds_poll(&L.pt.seq[0]);
-                    pcs = lds_poll(&L.pt.seq[1]);
-                    pv[0] = flag_load(pl.line(pt_progress_line(pl.side ^ 1)));
-                    pv[1] = flag_load(pl.line(pt_ready_line(pl.side * kPartnerSlots + (int)(pps % kPartnerSlots))));
-                    pv[2] = flag_load(pl.line(pt_ready_line((pl.side ^ 1) * kPartnerSlots + (int)(pcs % kPartnerSlots))));
-                }
-                ws_sync();  // hand-off of step k
-                ++nsync;
-            }
-            WSSTAMP(3, k);
-        }
-        if constexpr (kDealer) {  // no more batches; the last one lands before the state is stored
-            lds_publish(&L.dl.stop, 1u);
-            if (!faulted && !lds_wait_ge(L.dl, &L.dl.ddone, my_req)) faulted = true;
-            if (pool_stale && !faulted) {
-                pool = deal_of_lds(L.dl, lane);
-                pool_dirty = true;
-            }
-            if (faulted) {  // the tables' state is not stored: the host sees the fault and resets
-                signal_fault(S);
-                return;
-            }
-        }
-#ifdef SPL_STAMPS
-        {
-            const uint64_t clk1 = __builtin_amdgcn_s_memtime(), rt1 = __builtin_amdgcn_s_memrealtime();
-            if (g_wsclk && lane == 0) {
-                g_wsclk[sid * 4 + 0] = clk0;
-                g_wsclk[sid * 4 + 1] = rt0;
-                g_wsclk[sid * 4 + 2] = clk1;
-                g_wsclk[sid * 4 + 3] = rt1;
-            }
-        }
-        if (g_wsstamps && lane < K)
-            for (int i = 0; i < kWsStamps; ++i)
-                g_wsstamps[(((size_t)sid * 2 + 0) * 64 + lane) * kWsStamps + i] =
-                    ((uint64_t)(uint32_t)rst_hi[i] << 32) | (uint32_t)rst_lo[i];
-#endif
-        SPL_CHECK(kDealer || nsync == K, BC_BARRIER);
-        (void)nsync;
-        if (valid) {
-            if (S.next_actions) S.next_actions[t] = action;
-            store_tab(T, A, t, cur_mask, K > 0 ? Tb.mtag : 0u);  // cur_mask: the last step's mask of this state
-            if (pool_dirty) store_pool(A, t, pool);
-        }
-    } else {
-        const ColRecipes crc = col_recipes();  // this lane's bytes of a column-parallel terminal row
-        const uint64_t ply0 = S.ply + (S.ply_base ? *S.ply_base : 0ull);  // the policy words drawn ahead (dealer)
-        (void)ply0;
-#ifdef SPL_STAMPS
-        int rst_lo[kWsStamps] = {0}, rst_hi[kWsStamps] = {0};
-#endif
-        // delegation: both workgroups of a full pair take part (the same test on both sides)
-        Deleg dl{false, false, (int)(blockIdx.x >> 1), deleg_every, 0u};
-        if (deleg_shape && (int)(blockIdx.x | 1u) * 64 + 64 <= A.n) {
-            dl.on = true;
-            dl.producer = (blockIdx.x & 1u) != 0;
-            uint32_t *ep = A.dflags + (size_t)dl.pair * kDelegFlagWords + (dl.producer ? DF_PROD_EPOCH : DF_CONS_EPOCH) * kFlagLine;
-            dl.epoch = __builtin_amdgcn_readfirstlane(flag_load(ep)) + 1u;
-            flag_store(ep, dl.epoch);
-        }
-        uint32_t *const dflags = A.dflags + (size_t)dl.pair * kDelegFlagWords;
-        auto ready_flag = [&](int j) { return dflags + (DF_TASKS + 2 * j) * kFlagLine; };
-        auto taken_flag = [&](int j) { return dflags + (DF_TASKS + 2 * j + 1) * kFlagLine; };
-        auto slot_of = [&](int j) { return A.deleg + ((size_t)dl.pair * kDelegTasks + j) * kDelegPayload; };
-        int pend = -1, pend_k = -1;  // producer: task staged at step pend_k, ready flag not yet set
-        uint32_t staged = 0u;        // producer: tasks staged (not stored here)
-        // partner hand-off: tasks posted (pseq) and the one staged but not yet READY (ppend), partner
-        // tasks seen (cseq); the flags and the partner's progress come from the poller's LDS snapshots
-        uint32_t pseq = 0u, cseq = 0u;
-        int ppend = -1, ppend_k = 0;
-        uint32_t ppend_seen = 0u;  // the staged task's slot flag as the producer saw it (pt_post_ready)
-        int osync = 0;             // ws_sync() calls in the steps (the barrier invariant above)
-        for (int k = 0; k < K; ++k) {
-            if (pl.on) {
-                if (ppend >= 0) {  // the task staged last step: its words have completed, then READY
-                    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-                    pt_post_ready(pl.line(pt_ready_line(ppend)), pt_flag(pl.e, ppend_k, kPtReady), ppend_seen);
-                    ppend = -1;
-                }
-                // at most one of the partner's tasks per step, between this team's steps (the poller's
-                // snapshot of its next slot, if it is for the task this wave expects).  The quad kernel
-                // reads the snapshot its rules wave published at step k - 1, before the s_barrier of step
-                // k - 1 that this wave has passed (PtShared::qcons); the six-wave dealer acquires instead.
-                const uint64_t nx = kDealer ? lds_poll64(&L.pt.in[2]) : lds_poll64(&L.pt.qcons[(k + 1) & 1]);
-                if ((uint32_t)(nx >> 32) == cseq &&
-                    pt_serve_v<P>(pl, cseq, (uint32_t)nx, L.rows, L, S.obs, A.n, kDealer) && lane == 0)
-                    __hip_atomic_store(&L.pt.seq[1], cseq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-            if constexpr (kDealer) {
-                if (!lds_wait_ge(L.dl, &L.dl.rdone, (uint32_t)(k + 1))) {  // hand-off of step k
-                    // steps k.. are not stored: their flags say so (the blocks keep stale rows)
-                    for (int j = per_step ? k : 0; j < K && (per_step || j == 0); ++j)
-                        if (valid) S.flags[(per_step ? (size_t)j * (size_t)A.n : 0) + t] = (uint8_t)SPL_F_FAULT;
-                    // steps before k that were handed to the partner: DONE, and those it has not taken are
-                    // stored here (they were stepped before the fault)
-                    if (pl.on) pt_close<P>(pl, ppend, ppend_k, ppend_seen, pseq, L.rows, L, S.obs, A.n, t0);
-                    signal_fault(S);
-                    return;
-                }
-            } else {
-                ws_sync();  // hand-off of step k
-                ++osync;
-            }
-            WSSTAMP(0, k);
-            const int b = k & 1;
-            const size_t blk = per_step ? (size_t)k * (size_t)A.n : 0;
-            Tab<P> T;
-#pragma unroll
-            for (int w = 0; w < kW; ++w) set_tab_word(T, w, L.st[b][w][lane]);
-            // terminal rows (info["final_observation"]) first: each by the whole wave, column-parallel,
-            // straight from its listed state words (no staging, no LDS barrier)
-            // (readfirstlane returns int: widen through uint32_t, or bit 31 sign-extends into lanes 32-63)
-            uint64_t fin = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)L.fin[b]) |
-                           ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(L.fin[b] >> 32)) << 32);
-            if (fin) {
-                int32_t *fobs = S.final_obs + blk * kObsDim;
-                for (int idx = 0; fin; fin &= fin - 1, ++idx) {
-                    const int r = __ffsll((unsigned long long)fin) - 1;
-                    store_row_columns<P>(&L.tst[b][idx][0], 1, L, crc, fobs + (size_t)(t0 + r) * kObsDim);
-                }
-            }
-            const bool big_moves = __any(valid && get_moves(T.sw) > 255);
-            const bool deleg_now = dl.producer && deleg_step(k, K, dl.every);
-            bool handed = false;  // partner hand-off of this step's rows
-            uint32_t sf = 0u;     // the snapshot of the slot's flag it would go to
-            if (pl.on && !big_moves) {
-                const uint32_t pp = (uint32_t)lds_poll64(&L.pt.in[0]);
-                const uint64_t ms = lds_poll64(&L.pt.in[1]);
-                sf = (uint32_t)ms;
-                const bool ahead = pl.lead < 0 || ((pp >> 16) == pl.e && (int)(pp & 0xFFFFu) >= k + pl.lead);
-                // the slot is free (or stale), by a snapshot taken for this very slot
-                handed = ahead && (uint32_t)(ms >> 32) == pseq && ((sf & 3u) == 0u || (sf >> 16) != pl.e);
-            }
-            if (handed) {
-                const int j = pl.side * kPartnerSlots + (int)(pseq % kPartnerSlots);
-                stage_state(T, pl.slot(j));
-                ppend = j;
-                ppend_k = k;
-                ppend_seen = (uint32_t)__builtin_amdgcn_readfirstlane(sf);
-                ++pseq;
-                if (lane == 0) __hip_atomic_store(&L.pt.seq[0], pseq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            } else if (!deleg_now || big_moves) {  // a delegated step's rows are encoded by the partner
-                encode_row(T, L.rows, L);
-                wave_lds_sync();
-            }
-            WSSTAMP(1, k);
-            int32_t *obs = S.obs + blk * kObsDim;
-            if (handed) {
-            } else if (deleg_now) {
-                const int j = k / dl.every;
-                if (big_moves) {  // a patched row: stored here, the partner skips the task
-                    store_obs_block<TPW, true>(L.rows, rows, obs + (size_t)t0 * kObsDim);
-                    flag_store(ready_flag(j), dl.epoch << 1 | 1u);
-                } else {
-                    stage_state(T, slot_of(j));
-                    staged |= 1u << j;
-                    pend = j;
-                    pend_k = k;
-                }
-            } else if (abl(ABL_OBS_STORE)) {
-            } else {  // per-step blocks through the NT stream, in-place ones plain (kRollCpol's comment)
-                store_obs_block<TPW, per_step>(L.rows, rows, obs + (size_t)t0 * kObsDim);
-            }
-            WSSTAMP(2, k);
-            if (!abl(ABL_MASK_STORE)) store_mask_block<per_step>(L.mask[b], L.mbits, rows, S.mask + blk * 45 + (size_t)t0 * 45);
-            const uint32_t sm = L.small[b][lane];
-            if (sm & (1u << 9)) {  // valid lane: the rules wave's small outputs and episode statistics
-                if (!abl(ABL_SMALL_OUT)) {
-                    S.reward[blk + t] = reward_of_code((sm >> 13) & 7u);
-                    S.terminated[blk + t] = (uint8_t)((sm >> 8) & 1u);
-                    S.flags[blk + t] = (uint8_t)(sm & 0xFFu);
-                    if (S.winner) S.winner[blk + t] = (int8_t)((int)((sm >> 10) & 7u) - 1);
-                }
-                if (sm & (1u << 18)) {  // same per-table order and float rounding as step_ws
-                    if (S.ep_return) unsafeAtomicAdd(&S.ep_return[t], ep_of_code((sm >> 16) & 3u));
-                    if (S.ep_count) atomicAdd(&S.ep_count[t], 1u);
-                }
-            }
-            if (big_moves) {
-                __builtin_amdgcn_s_waitcnt(0);
-                if (valid && get_moves(T.sw) > 255) obs[(size_t)t * kObsDim + 295] = get_moves(T.sw);
-            }
-            if (pend >= 0 && k == pend_k + 2) {
-                // release (guide rule (2)): every sc1 store of the staged words has completed
-                // before the ready flag is stored; by now two steps of block stores sit behind
-                // them, so the wait also drains those
-                __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-                flag_store(ready_flag(pend), dl.epoch << 1);
-                pend = -1;
-            }
-            if constexpr (kDealer) {
-                if (S.policy == SPL_POLICY_UNIFORM && k + 2 < K)  // step k + 2's policy word, slot b again
-                    L.dl.rnd[b][lane] = uniform_draw(S.policy_seed, (uint64_t)(S.table0 + t), ply0 + (uint64_t)(k + 2));
-                lds_publish(&L.dl.odone, (uint32_t)(k + 1));  // slot b is free again
-            }
-            if (pl.on)  // this side's progress, for the partner's decisions (a write-through store, no wait)
-                flag_store(pl.line(pt_progress_line(pl.side)), pl.e << 16 | (uint32_t)(k + 1));
-            WSSTAMP(3, k);
-        }
-        SPL_CHECK(kDealer || osync == K, BC_BARRIER);
-        (void)osync;
-        if (pl.on) {
-            pt_close<P>(pl, ppend, ppend_k, ppend_seen, pseq, L.rows, L, S.obs, A.n, t0);
-            pt_drain<P>(pl, cseq, L.rows, L, S.obs, A.n);  // then the partner's, until it is done
-        }
-#ifdef SPL_STAMPS
-        if (g_wsend && lane == 0) g_wsend[sid * 2 + 0] = __builtin_amdgcn_s_memrealtime();
-#endif
-        if (dl.on && !dl.producer) {
-            // consumer: the partner's staged blocks, each as soon as its ready flag shows
-            const int64_t pt0 = (int64_t)(blockIdx.x + 1) * 64;
-            const uint64_t limit = 200000;  // 2 ms of s_memrealtime (100 MHz) per task at most
-            for (int k = 0; k < K; ++k) {
-                if (!deleg_step(k, K, dl.every)) continue;
-                const int j = k / dl.every;
-                uint32_t f = 0;
-                const uint64_t t_start = __builtin_amdgcn_s_memrealtime();
-                for (;;) {
-                    f = __builtin_amdgcn_readfirstlane(flag_load(ready_flag(j)));
-                    if ((f >> 1) == dl.epoch || __builtin_amdgcn_s_memrealtime() - t_start > limit) break;
-                    __builtin_amdgcn_s_sleep(8);
-                }
-                if ((f >> 1) != dl.epoch) break;  // not seen in time: the producer stores the rest
-                if (f & 1u) continue;              // the producer stored it
-                flag_store(taken_flag(j), dl.epoch);
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                Tab<P> T;
-                unstage_state(slot_of(j), T);
-                encode_row(T, L.rows, L);
-                wave_lds_sync();
-                store_obs_block<TPW, true>(L.rows, 64, S.obs + ((size_t)k * (size_t)A.n + pt0) * kObsDim);
-                wave_lds_sync();  // the block's LDS reads are done before the next task's rows land
-            }
-        }
-        if (dl.producer && staged) {
-            // producer: every staged block whose taken flag is not visible is stored here
-            for (int j = 0; j < kDelegTasks; ++j) {
-                if (!((staged >> j) & 1u)) continue;
-                const int k = j * dl.every + dl.every / 2 - 1;
-                if (__builtin_amdgcn_readfirstlane(flag_load(taken_flag(j))) == dl.epoch) continue;
-                Tab<P> T;
-                unstage_state(slot_of(j), T);
-                encode_row(T, L.rows, L);
-                wave_lds_sync();
-                store_obs_block<TPW, true>(L.rows, 64, S.obs + ((size_t)k * (size_t)A.n + t0) * kObsDim);
-                wave_lds_sync();
-            }
-        }
-#ifdef SPL_STAMPS
-        if (g_wsend) {
-            __builtin_amdgcn_s_waitcnt(0);  // this wave's stores have completed
-            if (lane == 0) g_wsend[sid * 2 + 1] = __builtin_amdgcn_s_memrealtime();
-        }
-#endif
-#ifdef SPL_STAMPS
-        if (g_wsstamps && lane < K)
-            for (int i = 0; i < kWsStamps; ++i)
-                g_wsstamps[(((size_t)sid * 2 + 1) * 64 + lane) * kWsStamps + i] =
-                    ((uint64_t)(uint32_t)rst_hi[i] << 32) | (uint32_t)rst_lo[i];
-#endif
-    }
+    if (w.role == 0) rules_wave<Sh>(L, A, Tb, S, K, refill, w, pl);
+    else output_wave<Sh>(L, A, S, K, extra, w, pl);
 }
 
-
-// The six-wave dealer variant (round 4; k_rollout_*_dealer2_<P>p, 128 tables per workgroup, one
-// workgroup per CU): two dealer-rollout teams (rules, output, dealer wave, 64 tables each) in ONE
-// workgroup, so the roles can be given to waves by the SIMD each one landed on.  With two 3-wave
+// The one-workgroup-per-CU variants: kTeams teams of rollout_ws in ONE workgroup, each on its own part
+// of the LDS, so the roles can be given to waves by the SIMD each one landed on; only which wave plays
+// which part changes, so results are those of every other rollout shape.
+//
+// The six-wave dealer variant (round 4; k_rollout_*_dealer2_<P>p, 128 tables per workgroup): two
+// dealer-rollout teams (rules, output, dealer wave, 64 tables each).  With two 3-wave
 // workgroups per CU the dispatcher's placement is blind to the roles: a rules wave — the latency-bound
 // critical path of the 4-player step — may share its SIMD with the other team's output or dealer
 // wave, and the 4-player C4 share's stamps showed the workgroups dispatched second on their CU
 // ending ~20 % after the first ones.  Here every wave reads its SIMD (HW_ID.SIMD_ID), the six are
 // exchanged through LDS, and all waves make the same choice: the two rules waves go to the least
-// occupied SIMDs (distinct ones), then the output waves, the dealers take the rest.  Each team is the
-// dealer rollout of rollout_ws on its own LDS half; only which wave plays which part changes, so
-// results are those of every other rollout shape.
-template <int P>
-struct __align__(16) WsDeal2LDS {
-    WsDealLDS<P> team[2];
-    uint32_t simd[6];
-};
-static_assert(sizeof(WsDeal2LDS<2>) <= 163840 && sizeof(WsDeal2LDS<3>) <= 163840 && sizeof(WsDeal2LDS<4>) <= 163840,
-              "the six-wave dealer rollout needs one workgroup per CU");
-
-// wave-uniform: (team * 3 + role) of wave w given the six waves' SIMDs.  Waves are taken in the
-// order (occupancy of their SIMD, wave index); each role takes two of them, preferring SIMDs that do
-// not hold a wave of that role yet: rules first, then output, then dealer.  Static indexing only.
-__device__ __forceinline__ int dealer2_assign(const uint32_t (&simd)[6], int w) {
-    int key[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        int occ = 0;
-#pragma unroll
-        for (int j = 0; j < 6; ++j) occ += simd[j] == simd[i] ? 1 : 0;
-        key[i] = occ * 8 + i;
-    }
-    int rank[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        int r = 0;
-#pragma unroll
-        for (int j = 0; j < 6; ++j) r += key[j] < key[i] ? 1 : 0;
-        rank[i] = r;
-    }
-    int code[6] = {-1, -1, -1, -1, -1, -1};
-#pragma unroll
-    for (int role = 0; role < 3; ++role) {
-        uint32_t used = 0u;  // SIMDs that already hold a wave of this role
-        int got = 0;
-#pragma unroll
-        for (int pass = 0; pass < 2; ++pass)
-#pragma unroll
-            for (int r = 0; r < 6; ++r)
-#pragma unroll
-                for (int i = 0; i < 6; ++i) {
-                    const bool take = rank[i] == r && got < 2 && code[i] < 0 &&
-                                      (pass == 1 || ((used >> (simd[i] & 3u)) & 1u) == 0u);
-                    code[i] = take ? got * 3 + role : code[i];
-                    used |= take ? 1u << (simd[i] & 3u) : 0u;
-                    got += take ? 1 : 0;
-                }
-    }
-    int mine = 0;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) mine = i == w ? code[i] : mine;
-    return mine;
-}
-
-template <int P, bool kStore>
-__device__ __forceinline__ void rollout_dealer2(WsDeal2LDS<P> &L, KArena A, KTables Tb, KStep S, int K, int refill,
-                                                int lead) {
-    const int w = (int)(threadIdx.x >> 6);
-    if (lane_id() == 0) L.simd[w] = (__builtin_amdgcn_s_getreg((31 << 11) | 4) >> 4) & 3u;
-    __syncthreads();
-    uint32_t simd[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) simd[i] = __builtin_amdgcn_readfirstlane(L.simd[i]);
-    const int code = __builtin_amdgcn_readfirstlane(dealer2_assign(simd, w));
-    const int team = code / 3;
-    rollout_ws<P, 64, kStore, true, WsDealLDS<P>, 2>(L.team[team], A, Tb, S, K, refill, lead,
-                                                      WaveRole{code % 3, 2 * wg_block() + team});
-}
-
-// The quad variant (round 5; k_rollout_*_quad_<P>p, 256 tables per workgroup, one workgroup per CU):
+// occupied SIMDs (distinct ones), then the output waves, the dealers take the rest.
+//
+// The quad variant (round 5; k_rollout_*_quad_<P>p, 256 tables per workgroup):
 // four two-wave teams (rules + output wave, 64 tables each) in ONE 512-thread workgroup — the
 // headline's 65 536 tables in 256 workgroups, all resident.  At one workgroup per CU the partner
 // hand-off (PartnerLink; the rules wave polls the pair's flag words, as it did in round 4's two-wave
@@ -3420,71 +3474,85 @@ __device__ __forceinline__ void rollout_dealer2(WsDeal2LDS<P> &L, KArena A, KTab
 // and loads, one signalling lane per storing wave after its vmcnt(0)), which the two-wave kernel at
 // four workgroups per CU was not.  Roles by SIMD as in the six-wave dealer: every
 // wave reads its SIMD, and the rules waves go to distinct SIMDs (each SIMD: one rules + one output
-// wave).  Each team is rollout_ws on its own LDS quarter; results are those of every other shape.
-template <int P>
-struct __align__(16) WsQuadLDS {
-    WsLDS<P> team[4];
-    uint32_t simd[8];
+// wave).
+template <class TeamLds, int kTeams>
+struct __align__(16) WsTeamsLDS {
+    TeamLds team[kTeams];
+    uint32_t simd[kTeams * TeamLds::kWaves];
 };
+template <int P>
+using WsDeal2LDS = WsTeamsLDS<WsDealLDS<P>, 2>;
+template <int P>
+using WsQuadLDS = WsTeamsLDS<WsLDS<P>, 4>;
+static_assert(sizeof(WsDeal2LDS<2>) <= 163840 && sizeof(WsDeal2LDS<3>) <= 163840 && sizeof(WsDeal2LDS<4>) <= 163840,
+              "the six-wave dealer rollout needs one workgroup per CU");
 static_assert(sizeof(WsQuadLDS<2>) <= 163840 && sizeof(WsQuadLDS<3>) <= 163840 && sizeof(WsQuadLDS<4>) <= 163840,
               "the quad rollout needs one workgroup per CU");
 
-// wave-uniform: (team * 2 + role) of wave w given the eight waves' SIMDs (dealer2_assign's rule for two
-// roles of four waves each: waves in the order (occupancy of their SIMD, index), rules first on distinct
-// SIMDs, then output).  Static indexing only.
-__device__ __forceinline__ int quad_assign(const uint32_t (&simd)[8], int w) {
-    int key[8];
+// wave-uniform: (team * kRoles + role) of wave w given the kWaves waves' SIMDs.  Waves are taken in the
+// order (occupancy of their SIMD, wave index); each role takes kWaves / kRoles of them, preferring SIMDs
+// that do not hold a wave of that role yet: rules first, then output, then (kRoles = 3) dealer.  Static
+// indexing only.
+template <int kWaves, int kRoles>
+__device__ __forceinline__ int team_assign(const uint32_t (&simd)[kWaves], int w) {
+    static_assert(kWaves <= 8 && kWaves % kRoles == 0, "the sort key holds 8 waves; whole teams");
+    int key[kWaves];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
+    for (int i = 0; i < kWaves; ++i) {
         int occ = 0;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) occ += simd[j] == simd[i] ? 1 : 0;
+        for (int j = 0; j < kWaves; ++j) occ += simd[j] == simd[i] ? 1 : 0;
         key[i] = occ * 8 + i;
     }
-    int rank[8];
+    int rank[kWaves];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
+    for (int i = 0; i < kWaves; ++i) {
         int r = 0;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) r += key[j] < key[i] ? 1 : 0;
+        for (int j = 0; j < kWaves; ++j) r += key[j] < key[i] ? 1 : 0;
         rank[i] = r;
     }
-    int code[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+    int code[kWaves];
 #pragma unroll
-    for (int role = 0; role < 2; ++role) {
-        uint32_t used = 0u;
+    for (int i = 0; i < kWaves; ++i) code[i] = -1;
+#pragma unroll
+    for (int role = 0; role < kRoles; ++role) {
+        uint32_t used = 0u;  // SIMDs that already hold a wave of this role
         int got = 0;
 #pragma unroll
         for (int pass = 0; pass < 2; ++pass)
 #pragma unroll
-            for (int r = 0; r < 8; ++r)
+            for (int r = 0; r < kWaves; ++r)
 #pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const bool take = rank[i] == r && got < 4 && code[i] < 0 &&
+                for (int i = 0; i < kWaves; ++i) {
+                    const bool take = rank[i] == r && got < kWaves / kRoles && code[i] < 0 &&
                                       (pass == 1 || ((used >> (simd[i] & 3u)) & 1u) == 0u);
-                    code[i] = take ? got * 2 + role : code[i];
+                    code[i] = take ? got * kRoles + role : code[i];
                     used |= take ? 1u << (simd[i] & 3u) : 0u;
                     got += take ? 1 : 0;
                 }
     }
     int mine = 0;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) mine = i == w ? code[i] : mine;
+    for (int i = 0; i < kWaves; ++i) mine = i == w ? code[i] : mine;
     return mine;
 }
 
-template <int P, bool kStore>
-__device__ __forceinline__ void rollout_quad(WsQuadLDS<P> &L, KArena A, KTables Tb, KStep S, int K, int refill, int lead) {
+template <int P, bool kStore, bool kDealer, int kTeams, class TeamLds>
+__device__ __forceinline__ void rollout_teams(WsTeamsLDS<TeamLds, kTeams> &L, KArena A, KTables Tb, KStep S, int K,
+                                              int refill, int lead) {
+    constexpr int kRoles = TeamLds::kWaves, kWaves = kTeams * kRoles;
+    static_assert(kRoles == (kDealer ? 3 : 2), "a dealer team has three waves, the others two");
     const int w = (int)(threadIdx.x >> 6);
     if (lane_id() == 0) L.simd[w] = (__builtin_amdgcn_s_getreg((31 << 11) | 4) >> 4) & 3u;
     __syncthreads();
-    uint32_t simd[8];
+    uint32_t simd[kWaves];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) simd[i] = __builtin_amdgcn_readfirstlane(L.simd[i]);
-    const int code = __builtin_amdgcn_readfirstlane(quad_assign(simd, w));
-    const int team = code >> 1;
-    rollout_ws<P, 64, kStore, false, WsLDS<P>, 4>(L.team[team], A, Tb, S, K, refill, lead,
-                                                  WaveRole{code & 1, 4 * wg_block() + team});
+    for (int i = 0; i < kWaves; ++i) simd[i] = __builtin_amdgcn_readfirstlane(L.simd[i]);
+    const int code = __builtin_amdgcn_readfirstlane(team_assign<kWaves, kRoles>(simd, w));
+    const int team = code / kRoles;
+    rollout_ws<P, 64, kStore, kDealer, TeamLds, kTeams>(L.team[team], A, Tb, S, K, refill, lead,
+                                                        WaveRole{code % kRoles, kTeams * wg_block() + team});
 }
 
 // Every multi-wave rollout kernel, one line each:
@@ -3517,18 +3585,18 @@ enum RolloutExtra { kExtraNone, kExtraDeleg, kExtraLead };
     X(k_rollout_store_dealer_2p, 192, 64, kExtraNone, WsDealLDS<2>, rollout_ws<2, 64, true, true>)    \
     X(k_rollout_store_dealer_3p, 192, 64, kExtraNone, WsDealLDS<3>, rollout_ws<3, 64, true, true>)    \
     X(k_rollout_store_dealer_4p, 192, 64, kExtraNone, WsDealLDS<4>, rollout_ws<4, 64, true, true>)    \
-    X(k_rollout_inplace_dealer2_2p, 384, 128, kExtraNone, WsDeal2LDS<2>, rollout_dealer2<2, false>)   \
-    X(k_rollout_inplace_dealer2_3p, 384, 128, kExtraNone, WsDeal2LDS<3>, rollout_dealer2<3, false>)   \
-    X(k_rollout_inplace_dealer2_4p, 384, 128, kExtraNone, WsDeal2LDS<4>, rollout_dealer2<4, false>)   \
-    X(k_rollout_store_dealer2_2p, 384, 128, kExtraLead, WsDeal2LDS<2>, rollout_dealer2<2, true>)      \
-    X(k_rollout_store_dealer2_3p, 384, 128, kExtraLead, WsDeal2LDS<3>, rollout_dealer2<3, true>)      \
-    X(k_rollout_store_dealer2_4p, 384, 128, kExtraLead, WsDeal2LDS<4>, rollout_dealer2<4, true>)      \
-    X(k_rollout_inplace_quad_2p, 512, 256, kExtraNone, WsQuadLDS<2>, rollout_quad<2, false>)          \
-    X(k_rollout_inplace_quad_3p, 512, 256, kExtraNone, WsQuadLDS<3>, rollout_quad<3, false>)          \
-    X(k_rollout_inplace_quad_4p, 512, 256, kExtraNone, WsQuadLDS<4>, rollout_quad<4, false>)          \
-    X(k_rollout_store_quad_2p, 512, 256, kExtraLead, WsQuadLDS<2>, rollout_quad<2, true>)             \
-    X(k_rollout_store_quad_3p, 512, 256, kExtraLead, WsQuadLDS<3>, rollout_quad<3, true>)             \
-    X(k_rollout_store_quad_4p, 512, 256, kExtraLead, WsQuadLDS<4>, rollout_quad<4, true>)
+    X(k_rollout_inplace_dealer2_2p, 384, 128, kExtraNone, WsDeal2LDS<2>, rollout_teams<2, false, true, 2>) \
+    X(k_rollout_inplace_dealer2_3p, 384, 128, kExtraNone, WsDeal2LDS<3>, rollout_teams<3, false, true, 2>) \
+    X(k_rollout_inplace_dealer2_4p, 384, 128, kExtraNone, WsDeal2LDS<4>, rollout_teams<4, false, true, 2>) \
+    X(k_rollout_store_dealer2_2p, 384, 128, kExtraLead, WsDeal2LDS<2>, rollout_teams<2, true, true, 2>) \
+    X(k_rollout_store_dealer2_3p, 384, 128, kExtraLead, WsDeal2LDS<3>, rollout_teams<3, true, true, 2>) \
+    X(k_rollout_store_dealer2_4p, 384, 128, kExtraLead, WsDeal2LDS<4>, rollout_teams<4, true, true, 2>) \
+    X(k_rollout_inplace_quad_2p, 512, 256, kExtraNone, WsQuadLDS<2>, rollout_teams<2, false, false, 4>) \
+    X(k_rollout_inplace_quad_3p, 512, 256, kExtraNone, WsQuadLDS<3>, rollout_teams<3, false, false, 4>) \
+    X(k_rollout_inplace_quad_4p, 512, 256, kExtraNone, WsQuadLDS<4>, rollout_teams<4, false, false, 4>) \
+    X(k_rollout_store_quad_2p, 512, 256, kExtraLead, WsQuadLDS<2>, rollout_teams<2, true, false, 4>) \
+    X(k_rollout_store_quad_3p, 512, 256, kExtraLead, WsQuadLDS<3>, rollout_teams<3, true, false, 4>) \
+    X(k_rollout_store_quad_4p, 512, 256, kExtraLead, WsQuadLDS<4>, rollout_teams<4, true, false, 4>)
 #define X(NAME, THREADS_, TPW_, EXTRA_, LDS_, ...)                                                                  \
     __global__ __launch_bounds__(THREADS_) void NAME(KArena A, KTables Tb, KStep S, int K, int refill, int extra) { \
         __shared__ LDS_ L;                                                                                          \
