@@ -1,0 +1,127 @@
+/*
+ * splendor_ppo.h — C-ABI of the PPO rollout store (gfx950): record, GAE and minibatch gather.
+ *
+ * The reference's learner (ppo_splendor.py:287-325) appends per-step numpy copies to Python lists,
+ * runs GAE as a numpy loop on the host and re-uploads everything for the update.  These entry points
+ * keep the agent's trajectory on the device in the engine's compact formats and reproduce the
+ * reference's arithmetic:
+ *
+ *   spl_ppo_record   one step's rows into a step-major store (compact observation rows copied, the
+ *                    int8 mask packed into 45-bit words, reward / done rows copied)
+ *   spl_ppo_gae      the reverse scan of ppo_splendor.py:304-314, bit-equal to numpy, plus the
+ *                    statistics ppo_splendor.py:325 normalises the advantages with
+ *   spl_ppo_gather   one minibatch of flat positions, expanded into what
+ *                    ActorCritic.get_action_and_value takes
+ *
+ * The store is step-major [K][T] (K steps, T tables), every plane caller-owned device memory:
+ *   obs_u8     uint8  [K][T][300]  the compact rows of spl_step_args_t.obs_u8 (bytes 0..296 the values
+ *                                  mod 256, byte 297 = move_count >> 8, bytes 298-299 zero)
+ *   mask_bits  uint64 [K][T]       bit a set <=> action a legal (bits 0..44, the rest zero)
+ *   action     int32  [K][T]
+ *   logprob, value, reward  float32 [K][T]
+ *   done       uint8  [K][T]       the dual step's `done`
+ *   adv, ret   float32 [K][T]      written by spl_ppo_gae
+ * action / logprob / value need no copy: spl_policy_act writes wherever it is pointed, so the
+ * collector points it at row k of the store.
+ *
+ * Conventions as in splendor_policy.h: caller-owned device buffers as raw pointers, `stream` a
+ * hipStream_t as void*, 0 / negative SPL_E_* returns, spl_last_error() for the message.  Argument
+ * errors are reported on the host before anything is launched.
+ */
+#ifndef SPLENDOR_PPO_H
+#define SPLENDOR_PPO_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define SPL_PPO_ABI 1
+
+#define SPL_PPO_OBS_U8 300 /* bytes of a compact observation row */
+
+/* spl_ppo_record: four source -> destination groups, each nullable as a pair (both NULL: the group
+ * is skipped; one NULL: SPL_E_ARG; all four skipped: SPL_E_ARG).  Destinations are row k of the
+ * store's planes. */
+typedef struct {
+    const uint8_t *obs_u8;   /* [n][300], 4-byte aligned                                            */
+    uint8_t *dst_obs_u8;     /* [n][300], 4-byte aligned (16-byte aligned pairs move 16 bytes a lane) */
+    const int8_t *mask;      /* [n][45] int8, nonzero = legal (spl_act_args_t.mask), any alignment   */
+    uint64_t *dst_mask_bits; /* [n], 8-byte aligned                                                  */
+    const float *reward;     /* [n], 4-byte aligned                                                  */
+    float *dst_reward;       /* [n], 4-byte aligned                                                  */
+    const uint8_t *done;     /* [n]                                                                  */
+    uint8_t *dst_done;       /* [n]                                                                  */
+} spl_ppo_record_t;
+
+/* Statistics of the float32 advantages x (as the adv plane holds them), accumulated in float64 in a
+ * fixed order (bit-identical from run to run):
+ *   count = K * T, sum = SUM x, sumsq = SUM x*x
+ *   mean  = sum / count
+ *   var   = (sumsq - sum * mean) / (count - 1)      the n-1 denominator of torch.std; a negative var
+ *   std   = sqrt(var < 0 ? 0 : var)                 (cancellation) counts as 0; count = 1 gives NaN
+ *   mean32 = (float)mean, std32 = (float)std
+ * every operation one IEEE float64 operation, left to right as written, none fused.  count, sum and
+ * sumsq are what sharded stores all-reduce. */
+typedef struct {
+    uint64_t count;
+    double sum, sumsq;
+    double mean, std;
+    float mean32, std32;
+} spl_ppo_stats_t;
+
+/* spl_ppo_gae: with r, v, v_next float32 and nnt = 1 - done[t] (v_next = last_value[table] at
+ * t = K-1, value[t+1] otherwise; `last` starts at 0 and is carried unrounded):
+ *   gv     = fp32( fp32(gamma) * v_next )
+ *   delta  = (f64)r + (f64)gv * nnt - (f64)v        float64, left to right
+ *   last   = delta + ((gamma * lambda) * nnt) * last      gamma * lambda multiplied once, in double
+ *   adv[t] = fp32(last);  ret[t] = fp32(last + (f64)v) */
+typedef struct {
+    const float *reward;     /* [K][T]                                                               */
+    const float *value;      /* [K][T]                                                               */
+    const uint8_t *done;     /* [K][T], nonzero = the episode ended on this step                     */
+    const float *last_value; /* [T]: the critic's value of the observation after step K-1            */
+    float *adv, *ret;        /* [K][T] out                                                           */
+    double gamma, lambda;    /* each in [0, 1]                                                       */
+    spl_ppo_stats_t *stats;  /* out, device, 8-byte aligned                                          */
+    void *scratch;           /* spl_ppo_gae_scratch_bytes(T) bytes, device, 8-byte aligned; no need to
+                                clear it: every word read was written by the same call               */
+} spl_ppo_gae_t;
+
+/* spl_ppo_gather: row b of every output is the store's flat position idx[b] = k * T + t (duplicates
+ * allowed).  A position outside [0, K*T) writes nothing for its row and adds one to *errors; its
+ * address is never formed. */
+typedef struct {
+    int32_t K, T;
+    int32_t normalize;            /* nonzero: adv = (adv - mean32) / (std32 + 1e-8f), each a correctly
+                                     rounded float32 operation, mean32 / std32 read from *stats on the
+                                     device; 0: the raw adv (stats may be NULL)                       */
+    int32_t reserved;             /* 0                                                               */
+    const int64_t *idx;           /* [B]                                                             */
+    const uint8_t *obs_u8;        /* the store's planes: [K][T][300], 4-byte aligned                 */
+    const uint64_t *mask_bits;    /* [K][T]                                                          */
+    const int32_t *action;        /* [K][T]                                                          */
+    const float *logprob, *value, *adv, *ret; /* [K][T]                                              */
+    const spl_ppo_stats_t *stats;
+    float *out_obs;               /* [B][297]: column 295 = byte 295 + 256 * byte 297, else its byte */
+    float *out_mask;              /* [B][45]: 0.0 / 1.0                                              */
+    int64_t *out_action;          /* [B]                                                             */
+    float *out_logprob, *out_value, *out_adv, *out_ret; /* [B]                                       */
+    uint64_t *errors;             /* device counter, incremented per bad position (never reset here) */
+} spl_ppo_gather_t;
+
+/* n rows of one step into the store */
+int spl_ppo_record(int32_t n, const spl_ppo_record_t *args, void *stream);
+/* bytes of spl_ppo_gae_t.scratch for T tables (SPL_E_ARG for T < 1) */
+int64_t spl_ppo_gae_scratch_bytes(int32_t T);
+/* advantages, returns and their statistics for a [K][T] store: two launches (the scan with each
+ * workgroup's partial sums, then a one-workgroup finish that combines them in a fixed order) */
+int spl_ppo_gae(int32_t K, int32_t T, const spl_ppo_gae_t *args, void *stream);
+/* one minibatch of B positions, expanded */
+int spl_ppo_gather(int32_t B, const spl_ppo_gather_t *args, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* SPLENDOR_PPO_H */

@@ -1,0 +1,362 @@
+// spl_ppo.hip — the PPO rollout store (include/splendor_ppo.h): record one step's rows, the GAE
+// reverse scan of ppo_splendor.py:304-314 with the advantage statistics of :325, and the minibatch
+// gather that expands the compact rows into ActorCritic.get_action_and_value's inputs.
+//
+// The GAE scan must be bit-equal to numpy, which never fuses a multiply with an add, while HIP device
+// code contracts a*b+c into an FMA by default.  Contraction is switched off for this whole file by
+// the pragma below (not by a Makefile flag: the requirement then travels with the source, whatever
+// builds it).
+#pragma clang fp contract(off)
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <string>
+
+#include "../../include/splendor_amd.h"
+#include "../../include/splendor_ppo.h"
+
+int spl_fail(int code, const std::string &msg);  // spl_engine.hip
+
+namespace splp {
+
+constexpr int kBlock = 256;
+
+// ---------------------------------------------------------------------------------------------
+// record
+// ---------------------------------------------------------------------------------------------
+struct Rec {
+    const uint32_t *obs;
+    uint32_t *dst_obs;
+    int64_t quads, tail;  // the rows as `quads` 16-byte pieces, then `tail` dwords
+    const int8_t *mask;
+    uint64_t *dst_mask;
+    const float *reward;
+    float *dst_reward;
+    const uint8_t *done;
+    uint8_t *dst_done;
+};
+
+// One launch for all four groups.  Rows: thread q moves 16-byte piece q (both sides 16-byte aligned;
+// else quads = 0 and every dword is a `tail` dword).  Masks: a wave owns 64 tables = 2 880 mask bytes,
+// read as 45 coalesced 64-byte loads; the ballot of "byte != 0" of load a is bits 64a..64a+63 of the
+// wave's 2 880-bit string, of which table L's word is bits 45L..45L+44.  The 45 ballots go through LDS
+// (lane a keeps ballot a) so that each lane can pick the two words its bits straddle.
+__global__ __launch_bounds__(kBlock) void k_record(int n, Rec r) {
+    __shared__ uint64_t words[kBlock / 64][64];
+    const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r.obs) {
+        if (q < r.quads) {
+            reinterpret_cast<uint4 *>(r.dst_obs)[q] = reinterpret_cast<const uint4 *>(r.obs)[q];
+        } else if (q < r.quads + r.tail) {
+            const int64_t e = 4 * r.quads + (q - r.quads);
+            r.dst_obs[e] = r.obs[e];
+        }
+    }
+    if ((int64_t)blockIdx.x * kBlock >= n) return;  // uniform over the workgroup
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (r.mask) {
+        const int64_t base = ((int64_t)blockIdx.x * kBlock + wave * 64) * 45, end = (int64_t)n * 45;
+        uint64_t mine = 0;
+#pragma unroll 5
+        for (int a = 0; a < 45; ++a) {
+            const int64_t off = base + a * 64 + lane;
+            const int8_t m = off < end ? r.mask[off] : (int8_t)0;
+            const uint64_t b = __ballot(m != 0);
+            if (lane == a) mine = b;
+        }
+        words[wave][lane] = lane < 45 ? mine : 0;
+        __syncthreads();
+        if (q < n) {
+            const int bit = 45 * lane, w = bit >> 6, s = bit & 63;  // w + 1 <= 45
+            const uint64_t lo = words[wave][w] >> s, hi = s ? words[wave][w + 1] << (64 - s) : 0;
+            r.dst_mask[q] = (lo | hi) & ((1ull << 45) - 1);
+        }
+    }
+    if (q < n) {
+        if (r.reward) r.dst_reward[q] = r.reward[q];
+        if (r.done) r.dst_done[q] = r.done[q];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// GAE
+// ---------------------------------------------------------------------------------------------
+// One lane per table, K dependent steps per lane.  At 65 536 tables there are four waves per CU, one
+// per SIMD, so nothing but the lane's own earlier loads can hide a load's latency: an HBM miss is
+// ~900 cycles (MI355X, idle chip), one step's dependent chain (a float multiply, five float64
+// operations, two conversions) is of the order of 60-100 cycles, so about a dozen steps have to be in
+// flight.  The scan therefore runs in chunks of kAhead = 8 steps with two register buffers: the loads of
+// the chunk after next are issued before the current chunk's chain starts, which keeps 8 to 16 steps
+// (24 to 48 loads, 48 VGPRs) ahead of the chain.
+constexpr int kAhead = 8;
+
+struct Chunk {
+    float r[kAhead], v[kAhead];
+    uint32_t d[kAhead];
+};
+
+struct Gae {
+    const float *reward, *value;
+    const uint8_t *done;
+    const float *last_value;
+    float *adv, *ret;
+    double gl;      // gamma * lambda, multiplied once on the host in double
+    float gamma_f;  // fp32(gamma)
+};
+
+// steps t0, t0 - 1, ... : `live` of them (kAhead in the pipelined loop; K % kAhead in the first, partial chunk)
+template <bool kFull>
+__device__ __forceinline__ void load_chunk(Chunk &c, const Gae &g, int t0, int live, int64_t T, int64_t i) {
+#pragma unroll
+    for (int j = 0; j < kAhead; ++j) {
+        if (kFull || j < live) {
+            const int64_t e = (int64_t)(t0 - j) * T + i;
+            c.r[j] = g.reward[e];
+            c.v[j] = g.value[e];
+            c.d[j] = g.done[e];
+        }
+    }
+}
+
+struct Scan {
+    double last, sum, sumsq;
+    float v_next;
+};
+
+template <bool kFull>
+__device__ __forceinline__ void scan_chunk(const Chunk &c, const Gae &g, int t0, int live, int64_t T, int64_t i, Scan &s) {
+#pragma unroll
+    for (int j = 0; j < kAhead; ++j) {
+        const int t = t0 - j;
+        if (kFull || j < live) {
+            const double nnt = c.d[j] ? 0.0 : 1.0;
+            const float gv = g.gamma_f * s.v_next;
+            const double v = (double)c.v[j];
+            const double delta = ((double)c.r[j] + (double)gv * nnt) - v;
+            s.last = delta + (g.gl * nnt) * s.last;
+            const float a = (float)s.last;
+            const int64_t e = (int64_t)t * T + i;
+            g.adv[e] = a;
+            g.ret[e] = (float)(s.last + v);
+            s.sum += (double)a;
+            s.sumsq += (double)a * (double)a;
+            s.v_next = c.v[j];
+        }
+    }
+}
+
+// sum of x over the workgroup in a fixed order (a binary tree over the lane index); result in lane 0
+__device__ __forceinline__ double block_sum(double x, double *lds) {
+    lds[threadIdx.x] = x;
+    __syncthreads();
+#pragma unroll
+    for (int h = kBlock / 2; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) lds[threadIdx.x] += lds[threadIdx.x + h];
+        __syncthreads();
+    }
+    const double r = lds[0];
+    __syncthreads();
+    return r;
+}
+
+__global__ __launch_bounds__(kBlock) void k_gae(int K, int T, Gae g, double *__restrict__ partial) {
+    __shared__ double lds[kBlock];
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    Scan s{0.0, 0.0, 0.0, 0.f};
+    if (i < T) {
+        s.v_next = g.last_value[i];
+        // the K % kAhead newest steps as one partial chunk, then whole chunks only: chunk c (1-based)
+        // holds steps kAhead * c - 1 down to kAhead * (c - 1)
+        Chunk a, b;
+        const int rem = K % kAhead;
+        int c = K / kAhead;
+        if (rem) load_chunk<false>(b, g, K - 1, rem, T, i);
+        if (c >= 1) load_chunk<true>(a, g, kAhead * c - 1, kAhead, T, i);
+        if (rem) scan_chunk<false>(b, g, K - 1, rem, T, i, s);
+        for (; c >= 2; c -= 2) {
+            load_chunk<true>(b, g, kAhead * (c - 1) - 1, kAhead, T, i);
+            scan_chunk<true>(a, g, kAhead * c - 1, kAhead, T, i, s);
+            if (c >= 3) load_chunk<true>(a, g, kAhead * (c - 2) - 1, kAhead, T, i);
+            scan_chunk<true>(b, g, kAhead * (c - 1) - 1, kAhead, T, i, s);
+        }
+        if (c == 1) scan_chunk<true>(a, g, kAhead - 1, kAhead, T, i, s);
+    }
+    const double sum = block_sum(s.sum, lds), sumsq = block_sum(s.sumsq, lds);
+    if (threadIdx.x == 0) {
+        partial[2 * blockIdx.x] = sum;
+        partial[2 * blockIdx.x + 1] = sumsq;
+    }
+}
+
+// one workgroup: lane j adds partials j, j + 256, ... in that order, then the same tree
+__global__ __launch_bounds__(kBlock) void k_gae_finish(int blocks, uint64_t count, const double *__restrict__ partial,
+                                                       spl_ppo_stats_t *__restrict__ st) {
+    __shared__ double lds[kBlock];
+    double s = 0.0, ss = 0.0;
+    for (int p = threadIdx.x; p < blocks; p += kBlock) {
+        s += partial[2 * p];
+        ss += partial[2 * p + 1];
+    }
+    const double sum = block_sum(s, lds), sumsq = block_sum(ss, lds);
+    if (threadIdx.x == 0) {
+        const double n = (double)count;
+        const double mean = sum / n;
+        double var = (sumsq - sum * mean) / (n - 1.0);
+        if (var < 0.0) var = 0.0;  // a NaN (count = 1) stays a NaN
+        const double sd = sqrt(var);
+        st->count = count;
+        st->sum = sum;
+        st->sumsq = sumsq;
+        st->mean = mean;
+        st->std = sd;
+        st->mean32 = (float)mean;
+        st->std32 = (float)sd;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// gather
+// ---------------------------------------------------------------------------------------------
+// One wave per row, four rows per workgroup.  In: the row's 75 dwords as two coalesced dword loads
+// (lanes 0..63, then lanes 0..10) into LDS.  Out: lane j converts bytes j, j + 64, ... so that every
+// store instruction of the wave writes 64 consecutive floats (297 floats in five stores, the 45 mask
+// floats in one); rows of 297 floats are only 4-byte aligned, so dwords are the widest store.
+__global__ __launch_bounds__(kBlock) void k_gather(int B, int64_t total, spl_ppo_gather_t g) {
+    __shared__ uint32_t rows[kBlock / 64][76];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t b = (int64_t)blockIdx.x * (kBlock / 64) + wave;
+    const int64_t pos = b < B ? g.idx[b] : -1;
+    const bool ok = b < B && pos >= 0 && pos < total;  // the address is formed only under `ok`
+    if (ok) {
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(g.obs_u8 + pos * SPL_PPO_OBS_U8);
+        rows[wave][lane] = src[lane];
+        if (lane < 75 - 64) rows[wave][64 + lane] = src[64 + lane];
+    }
+    __syncthreads();
+    if (!ok) {
+        if (b < B && lane == 0) atomicAdd(reinterpret_cast<unsigned long long *>(g.errors), 1ull);
+        return;
+    }
+    const uint8_t *rb = reinterpret_cast<const uint8_t *>(rows[wave]);
+    const uint32_t hi = rb[297];
+    float *o = g.out_obs + b * 297;
+#pragma unroll
+    for (int m = 0; m < 5; ++m) {
+        const int c = lane + 64 * m;
+        if (c < 297) {
+            uint32_t x = rb[c];
+            if (c == 295) x += hi << 8;  // move_count
+            o[c] = (float)x;
+        }
+    }
+    const uint64_t bits = g.mask_bits[pos];
+    if (lane < 45) g.out_mask[b * 45 + lane] = ((bits >> lane) & 1) ? 1.f : 0.f;
+    if (lane == 0) g.out_action[b] = (int64_t)g.action[pos];
+    if (lane == 1) g.out_logprob[b] = g.logprob[pos];
+    if (lane == 2) g.out_value[b] = g.value[pos];
+    if (lane == 3) g.out_ret[b] = g.ret[pos];
+    if (lane == 4) {
+        float a = g.adv[pos];
+        if (g.normalize) {
+            // float32 subtract and add are single IEEE operations; the quotient is taken in float64
+            // and rounded once more, which for float32 operands equals the correctly rounded float32
+            // quotient (53 >= 2 * 24 + 2)
+            const float num = a - g.stats->mean32, den = g.stats->std32 + 1e-8f;
+            a = (float)((double)num / (double)den);
+        }
+        g.out_adv[b] = a;
+    }
+}
+
+static int launched(const char *what) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SPL_OK : spl_fail(SPL_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+static bool misaligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
+
+}  // namespace splp
+
+using namespace splp;
+
+extern "C" {
+
+int spl_ppo_record(int32_t n, const spl_ppo_record_t *a, void *stream) {
+    if (n <= 0) return spl_fail(SPL_E_ARG, "n must be positive");
+    if (!a) return spl_fail(SPL_E_ARG, "null record arguments");
+    if (!a->obs_u8 != !a->dst_obs_u8 || !a->mask != !a->dst_mask_bits || !a->reward != !a->dst_reward ||
+        !a->done != !a->dst_done)
+        return spl_fail(SPL_E_ARG, "null buffer: a record group needs its source and its destination");
+    if (!a->obs_u8 && !a->mask && !a->reward && !a->done) return spl_fail(SPL_E_ARG, "null buffer: nothing to record");
+    if (misaligned(a->obs_u8, 4) || misaligned(a->dst_obs_u8, 4))
+        return spl_fail(SPL_E_ARG, "obs_u8 rows must be 4-byte aligned");
+    if (misaligned(a->dst_mask_bits, 8)) return spl_fail(SPL_E_ARG, "mask_bits must be 8-byte aligned");
+    if (misaligned(a->reward, 4) || misaligned(a->dst_reward, 4))
+        return spl_fail(SPL_E_ARG, "reward rows must be 4-byte aligned");
+    Rec r{};
+    const int64_t dwords = (int64_t)n * (SPL_PPO_OBS_U8 / 4);
+    if (a->obs_u8) {
+        r.obs = reinterpret_cast<const uint32_t *>(a->obs_u8);
+        r.dst_obs = reinterpret_cast<uint32_t *>(a->dst_obs_u8);
+        const bool wide = !misaligned(a->obs_u8, 16) && !misaligned(a->dst_obs_u8, 16);
+        r.quads = wide ? dwords / 4 : 0;
+        r.tail = dwords - 4 * r.quads;
+    }
+    r.mask = a->mask;
+    r.dst_mask = a->dst_mask_bits;
+    r.reward = a->reward;
+    r.dst_reward = a->dst_reward;
+    r.done = a->done;
+    r.dst_done = a->dst_done;
+    const int64_t items = r.quads + r.tail, threads = items > n ? items : (int64_t)n;
+    hipLaunchKernelGGL(k_record, dim3((unsigned)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream,
+                       n, r);
+    return launched("k_record");
+}
+
+int64_t spl_ppo_gae_scratch_bytes(int32_t T) {
+    if (T < 1) return spl_fail(SPL_E_ARG, "T must be positive");
+    return (int64_t)((T + kBlock - 1) / kBlock) * 2 * (int64_t)sizeof(double);
+}
+
+int spl_ppo_gae(int32_t K, int32_t T, const spl_ppo_gae_t *a, void *stream) {
+    if (K < 1 || T < 1) return spl_fail(SPL_E_ARG, "K and T must be positive");
+    if (!a) return spl_fail(SPL_E_ARG, "null gae arguments");
+    if (!a->reward || !a->value || !a->done || !a->last_value || !a->adv || !a->ret || !a->stats || !a->scratch)
+        return spl_fail(SPL_E_ARG, "null buffer");
+    if (!(a->gamma >= 0.0 && a->gamma <= 1.0) || !(a->lambda >= 0.0 && a->lambda <= 1.0))
+        return spl_fail(SPL_E_ARG, "gamma and lambda must be in [0, 1]");
+    if (misaligned(a->reward, 4) || misaligned(a->value, 4) || misaligned(a->last_value, 4) || misaligned(a->adv, 4) ||
+        misaligned(a->ret, 4) || misaligned(a->stats, 8) || misaligned(a->scratch, 8))
+        return spl_fail(SPL_E_ARG, "float planes must be 4-byte aligned, stats and scratch 8-byte aligned");
+    const Gae g{a->reward, a->value, a->done, a->last_value, a->adv, a->ret, a->gamma * a->lambda, (float)a->gamma};
+    const int blocks = (T + kBlock - 1) / kBlock;
+    const hipStream_t s = (hipStream_t)stream;
+    double *partial = static_cast<double *>(a->scratch);
+    hipLaunchKernelGGL(k_gae, dim3(blocks), dim3(kBlock), 0, s, K, T, g, partial);
+    hipLaunchKernelGGL(k_gae_finish, dim3(1), dim3(kBlock), 0, s, blocks, (uint64_t)K * (uint64_t)T, partial, a->stats);
+    return launched("k_gae");
+}
+
+int spl_ppo_gather(int32_t B, const spl_ppo_gather_t *a, void *stream) {
+    if (B <= 0) return spl_fail(SPL_E_ARG, "B must be positive");
+    if (!a) return spl_fail(SPL_E_ARG, "null gather arguments");
+    if (a->K < 1 || a->T < 1) return spl_fail(SPL_E_ARG, "K and T must be positive");
+    if (!a->idx || !a->obs_u8 || !a->mask_bits || !a->action || !a->logprob || !a->value || !a->adv || !a->ret ||
+        !a->out_obs || !a->out_mask || !a->out_action || !a->out_logprob || !a->out_value || !a->out_adv ||
+        !a->out_ret || !a->errors || (a->normalize && !a->stats))
+        return spl_fail(SPL_E_ARG, "null buffer");
+    if (misaligned(a->obs_u8, 4)) return spl_fail(SPL_E_ARG, "obs_u8 rows must be 4-byte aligned");
+    if (misaligned(a->idx, 8) || misaligned(a->mask_bits, 8) || misaligned(a->out_action, 8) ||
+        misaligned(a->errors, 8) || misaligned(a->stats, 8))
+        return spl_fail(SPL_E_ARG, "idx, mask_bits, out_action, errors and stats must be 8-byte aligned");
+    if (misaligned(a->out_obs, 4) || misaligned(a->out_mask, 4))
+        return spl_fail(SPL_E_ARG, "float outputs must be 4-byte aligned");
+    const int rows = kBlock / 64;
+    hipLaunchKernelGGL(k_gather, dim3((unsigned)((B + rows - 1) / rows)), dim3(kBlock), 0, (hipStream_t)stream, B,
+                       (int64_t)a->K * a->T, *a);
+    return launched("k_gather");
+}
+
+}  // extern "C"

@@ -77,6 +77,33 @@ class DualDraw(ctypes.Structure):
 DUAL_ILLEGAL, DUAL_DRAW, DUAL_TURN_LIMIT = 0x01, 0x02, 0x04  # SPL_DUAL_*
 
 
+class PpoRecord(ctypes.Structure):
+    """spl_ppo_record_t (include/splendor_ppo.h)"""
+    _fields_ = [(k, c_void_p) for k in ("obs_u8", "dst_obs_u8", "mask", "dst_mask_bits", "reward", "dst_reward",
+                                        "done", "dst_done")]
+
+
+class PpoStats(ctypes.Structure):
+    """spl_ppo_stats_t (include/splendor_ppo.h)"""
+    _fields_ = [("count", c_uint64), ("sum", ctypes.c_double), ("sumsq", ctypes.c_double), ("mean", ctypes.c_double),
+                ("std", ctypes.c_double), ("mean32", ctypes.c_float), ("std32", ctypes.c_float)]
+
+
+class PpoGae(ctypes.Structure):
+    """spl_ppo_gae_t (include/splendor_ppo.h)"""
+    _fields_ = [("reward", c_void_p), ("value", c_void_p), ("done", c_void_p), ("last_value", c_void_p),
+                ("adv", c_void_p), ("ret", c_void_p), ("gamma", ctypes.c_double), ("lam", ctypes.c_double),
+                ("stats", c_void_p), ("scratch", c_void_p)]
+
+
+class PpoGather(ctypes.Structure):
+    """spl_ppo_gather_t (include/splendor_ppo.h)"""
+    _fields_ = [("K", c_int32), ("T", c_int32), ("normalize", c_int32), ("reserved", c_int32)] + \
+               [(k, c_void_p) for k in ("idx", "obs_u8", "mask_bits", "action", "logprob", "value", "adv", "ret", "stats",
+                                        "out_obs", "out_mask", "out_action", "out_logprob", "out_value", "out_adv",
+                                        "out_ret", "errors")]
+
+
 # spl_table_t (include/splendor_table.h) as a numpy structured dtype
 PLAYER_DTYPE = np.dtype([("tokens", "<i4", 6), ("bonuses", "<i4", 5), ("prestige", "<i4"),
                          ("n_reserved", "<i4"), ("reserved", "<i4", 3), ("revealed", "<i4", 3),
@@ -141,6 +168,11 @@ SIGNATURES = {
     "spl_policy_group_scratch_bytes": ([c_int32, c_int32], c_int64),
     "spl_policy_act_grouped": ([c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int32, ctypes.POINTER(ActArgs),
                                 c_void_p], c_int32),
+    # include/splendor_ppo.h
+    "spl_ppo_record": ([c_int32, ctypes.POINTER(PpoRecord), c_void_p], c_int32),
+    "spl_ppo_gae_scratch_bytes": ([c_int32], c_int64),
+    "spl_ppo_gae": ([c_int32, c_int32, ctypes.POINTER(PpoGae), c_void_p], c_int32),
+    "spl_ppo_gather": ([c_int32, ctypes.POINTER(PpoGather), c_void_p], c_int32),
 }
 
 

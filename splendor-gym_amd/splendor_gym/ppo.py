@@ -1,0 +1,259 @@
+"""The PPO rollout store on the device (include/splendor_ppo.h): record, GAE, minibatch gather, and a
+collector and update loop on top.
+
+The reference's learner (ppo_splendor.py:287-325) appends per-step numpy copies to Python lists, runs
+GAE as a numpy loop on the host and re-uploads everything for the update.  Here the agent's trajectory
+stays on the device, step-major [K][T] in the engine's compact formats (uint8 observation rows, 45-bit
+masks: 2.8 GB instead of 10.4 GB at 128 steps x 65 536 tables):
+
+  * ``PPORolloutStore``  the planes, ``record_pre`` / ``record_post`` / ``row`` to fill row k around a
+    dual step, ``compute_gae`` (ppo_splendor.py:304-314, bit-equal to the numpy loop, and the mean and
+    n-1 standard deviation ppo_splendor.py:325 normalises with), ``gather`` (one minibatch expanded
+    into ``ActorCritic.get_action_and_value``'s float32 inputs) and ``minibatches``;
+  * ``collect``  num_steps iterations of the config-5 loop (FusedActorCritic.act on the env's compact
+    rows, DualStepVectorEnv.dual_step), recorded, and the bootstrap value; eager or one hipGraph;
+  * ``ppo_update``  the update of ppo_splendor.py:327-361 in torch over ``store.minibatches``.
+
+The learner's forward and backward passes stay in torch.  There is no CPU fallback.
+"""
+import ctypes
+
+from . import _native
+from ._native import NUM_ACTIONS, OBS_DIM, OBS_U8, PpoGae, PpoGather, PpoRecord, check
+
+
+class PPORolloutStore:
+    """Step-major planes of one rollout (num_steps x num_envs), as torch tensors on `device`:
+    obs_u8 uint8 [K, T, 300], mask_bits int64 [K, T] (the uint64 words of the ABI), action int32,
+    logprob / value / reward / adv / ret float32, done uint8 [K, T]; last_value float32 [T] (the
+    bootstrap value collect() leaves); errors int64 [1] (bad positions seen by gather)."""
+
+    def __init__(self, num_steps, num_envs, device):
+        torch = _native.require_gpu()
+        self.torch = torch
+        self.lib = _native.load_library()
+        K, T = int(num_steps), int(num_envs)
+        if K < 1 or T < 1:
+            raise ValueError("num_steps and num_envs must be positive")
+        self.num_steps, self.num_envs = K, T
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("PPORolloutStore lives on a GPU (no CPU fallback)")
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self.device)
+        self.obs_u8 = z((K, T, OBS_U8), torch.uint8)
+        self.mask_bits = z((K, T), torch.int64)
+        self.action = z((K, T), torch.int32)
+        self.logprob, self.value, self.reward = (z((K, T), torch.float32) for _ in range(3))
+        self.done = z((K, T), torch.uint8)
+        self.adv, self.ret = z((K, T), torch.float32), z((K, T), torch.float32)
+        self.last_value = z((T,), torch.float32)
+        self.errors = z((1,), torch.int64)
+        self._entropy = z((T,), torch.float32)  # act() writes it; the update recomputes the entropy
+        self._stats = z((6,), torch.float64)    # spl_ppo_stats_t: count, sum, sumsq, mean, std, {mean32, std32}
+        self.mean32 = self._stats.view(torch.float32)[10:11]  # device views for tests and sharded all-reduces
+        self.std32 = self._stats.view(torch.float32)[11:12]
+        self._scratch = z((int(check(self.lib, self.lib.spl_ppo_gae_scratch_bytes(T))) // 8,), torch.float64)
+
+    def _stream(self):
+        return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _own(self, x, dtypes, shape, what):
+        if x.dtype not in dtypes or tuple(x.shape) != shape or not x.is_contiguous() or x.device != self.device:
+            raise ValueError(f"{what} must be a contiguous {dtypes[0]} {list(shape)} tensor on {self.device}")
+        return x
+
+    def _record(self, **kw):
+        with self.torch.cuda.device(self.device):
+            check(self.lib, self.lib.spl_ppo_record(self.num_envs, ctypes.byref(PpoRecord(**kw)), self._stream()))
+
+    def record_pre(self, k, obs_u8, mask):
+        """Row k's observation (the compact uint8 [T, 300] rows) and legal mask (int8 [T, 45], nonzero =
+        legal): call before the dual step that consumes them."""
+        t, T = self.torch, self.num_envs
+        self._own(obs_u8, (t.uint8,), (T, OBS_U8), "obs_u8")
+        self._own(mask, (t.int8, t.uint8, t.bool), (T, NUM_ACTIONS), "mask")
+        self._record(obs_u8=obs_u8.data_ptr(), dst_obs_u8=self.obs_u8[k].data_ptr(), mask=mask.data_ptr(),
+                     dst_mask_bits=self.mask_bits[k].data_ptr())
+
+    def record_post(self, k, reward, done):
+        """Row k's reward (float32 [T]) and done (one byte per table) as the dual step returned them."""
+        t, T = self.torch, self.num_envs
+        self._own(reward, (t.float32,), (T,), "reward")
+        self._own(done, (t.uint8, t.bool, t.int8), (T,), "done")
+        self._record(reward=reward.data_ptr(), dst_reward=self.reward[k].data_ptr(), done=done.data_ptr(),
+                     dst_done=self.done[k].data_ptr())
+
+    def row(self, k):
+        """The out= dict that points FusedActorCritic.act at row k (value as the [T, 1] view)."""
+        return {"action": self.action[k], "logprob": self.logprob[k], "value": self.value[k].view(self.num_envs, 1),
+                "entropy": self._entropy}
+
+    def compute_gae(self, last_value=None, gamma=0.999, gae_lambda=0.95):
+        """adv, ret and the advantage statistics (asynchronous).  last_value: float32 [T] or [T, 1], the
+        critic's value after the last step (default: self.last_value, which collect() fills)."""
+        t, T = self.torch, self.num_envs
+        lv = self.last_value if last_value is None else last_value
+        if lv.dim() == 2 and lv.shape[1] == 1:
+            lv = lv.view(-1)
+        self._own(lv, (t.float32,), (T,), "last_value")
+        a = PpoGae(reward=self.reward.data_ptr(), value=self.value.data_ptr(), done=self.done.data_ptr(),
+                   last_value=lv.data_ptr(), adv=self.adv.data_ptr(), ret=self.ret.data_ptr(), gamma=float(gamma),
+                   lam=float(gae_lambda), stats=self._stats.data_ptr(), scratch=self._scratch.data_ptr())
+        with t.cuda.device(self.device):
+            check(self.lib, self.lib.spl_ppo_gae(self.num_steps, T, ctypes.byref(a), self._stream()))
+        self._keep = lv
+        return self.adv, self.ret
+
+    def stats(self):
+        """The statistics of the last compute_gae as Python numbers (synchronises): count, sum, sumsq,
+        mean, std (float64; n-1 denominator) and mean32, std32 (their float32 roundings)."""
+        s = self._stats.cpu()
+        f = s.view(self.torch.float32)
+        return {"count": int(s.view(self.torch.int64)[0]), "sum": float(s[1]), "sumsq": float(s[2]), "mean": float(s[3]),
+                "std": float(s[4]), "mean32": float(f[10]), "std32": float(f[11])}
+
+    def gather(self, idx, normalize=True, out=None):
+        """The minibatch of flat positions idx (int64 [B], k * T + t): obs float32 [B, 297], mask float32
+        [B, 45], action int64 [B], logprob / value / adv / ret float32 [B].  adv is normalised with the
+        store's mean32 / std32 on the device when `normalize`.  A position outside the store leaves its
+        rows as they were and counts in self.errors."""
+        t = self.torch
+        if idx.dtype != t.int64 or idx.dim() != 1 or not idx.is_contiguous() or idx.device != self.device or \
+                idx.numel() < 1:
+            raise ValueError(f"idx must be a non-empty contiguous int64 [B] tensor on {self.device}")
+        B = idx.numel()
+        if out is None:
+            e = lambda shape, dt: t.empty(shape, dtype=dt, device=self.device)
+            out = {"obs": e((B, OBS_DIM), t.float32), "mask": e((B, NUM_ACTIONS), t.float32), "action": e((B,), t.int64),
+                   "logprob": e((B,), t.float32), "value": e((B,), t.float32), "adv": e((B,), t.float32),
+                   "ret": e((B,), t.float32)}
+        else:
+            self._own(out["obs"], (t.float32,), (B, OBS_DIM), "out['obs']")
+            self._own(out["mask"], (t.float32,), (B, NUM_ACTIONS), "out['mask']")
+            self._own(out["action"], (t.int64,), (B,), "out['action']")
+            for name in ("logprob", "value", "adv", "ret"):
+                self._own(out[name], (t.float32,), (B,), f"out['{name}']")
+        a = PpoGather(K=self.num_steps, T=self.num_envs, normalize=1 if normalize else 0, reserved=0,
+                      idx=idx.data_ptr(), obs_u8=self.obs_u8.data_ptr(), mask_bits=self.mask_bits.data_ptr(),
+                      action=self.action.data_ptr(), logprob=self.logprob.data_ptr(), value=self.value.data_ptr(),
+                      adv=self.adv.data_ptr(), ret=self.ret.data_ptr(), stats=self._stats.data_ptr(),
+                      out_obs=out["obs"].data_ptr(), out_mask=out["mask"].data_ptr(),
+                      out_action=out["action"].data_ptr(), out_logprob=out["logprob"].data_ptr(),
+                      out_value=out["value"].data_ptr(), out_adv=out["adv"].data_ptr(), out_ret=out["ret"].data_ptr(),
+                      errors=self.errors.data_ptr())
+        with t.cuda.device(self.device):
+            check(self.lib, self.lib.spl_ppo_gather(B, ctypes.byref(a), self._stream()))
+        return out
+
+    def minibatches(self, batch_size, generator=None):
+        """One epoch's index tensors: a device randperm of the K * T positions split into pieces of
+        batch_size, the last one shorter (ppo_splendor.py:334-336)."""
+        total = self.num_steps * self.num_envs
+        bs = min(int(batch_size), total)
+        perm = self.torch.randperm(total, device=self.device, generator=generator)
+        for start in range(0, total, bs):
+            yield perm[start:start + bs]
+
+
+def _iterations(env, agent_k, store, mask, seed, table0):
+    obs = None
+    for k in range(store.num_steps):
+        store.record_pre(k, env.agent_obs_u8, mask)
+        action = agent_k.act(env.agent_obs_u8, mask, seed=seed, table0=table0, ply_base=env._step_counter,
+                             out=store.row(k))[0]
+        obs, reward, _, _, done, info = env.dual_step(action)
+        mask = info["action_mask"]
+        store.record_post(k, reward, done)
+    agent_k.get_value(obs, out=store.last_value.view(store.num_envs, 1))
+    return obs, mask
+
+
+def collect(env, agent_k, store, obs, mask, seed=0, table0=0, graph=False):
+    """store.num_steps iterations of the config-5 loop (tools/bench_selfplay.py): FusedActorCritic.act on
+    env.agent_obs_u8 with the env's device step counter as ply_base, written straight into row k of the
+    store, then env.dual_step; observation, mask, reward and done recorded around it.  Afterwards
+    store.last_value holds agent_k.get_value of the final observations (the bootstrap value of
+    ppo_splendor.py:302).  Returns the new (obs, mask).
+
+    env: a DualStepVectorEnv built with agent_obs_u8=True and a step_counter; obs / mask: what its
+    reset() or the previous collect() returned (the env's own buffers).
+
+    graph=True runs the first call eagerly, captures the K iterations as one linear, single-stream
+    hipGraph, and replays it on later calls.  The agent's draws are keyed by the device step counter, so a replay draws
+    what the eager loop would.  A device-policy opponent ("random", ...) takes its ply from the host, which
+    a replay cannot advance, so graph=True refuses it.  A capture holds the opponent pool's size: it is
+    taken again after add_snapshot() changed it."""
+    torch = store.torch
+    if env.agent_obs_u8 is None or env._step_counter is None:
+        raise ValueError("collect needs a DualStepVectorEnv built with agent_obs_u8=True and a step_counter")
+    if env.num_envs != store.num_envs:
+        raise ValueError("the store and the env must hold the same number of tables")
+    if obs.data_ptr() != env.eng.obs.data_ptr() or mask.data_ptr() != env.eng.mask.data_ptr():
+        raise ValueError("obs and mask must be the env's own buffers (what reset() or collect() returned)")
+    with torch.no_grad():
+        if not graph:
+            return _iterations(env, agent_k, store, mask, seed, table0)
+        if isinstance(env.opponent, str):
+            raise ValueError("collect(graph=True) needs a network opponent: a device-policy opponent's draws are keyed "
+                             "by a host-side ply that a replayed graph would repeat")
+        pool = env.pool
+        key = (id(env), id(agent_k), int(seed), int(table0), None if pool is None else (len(pool.pool), pool.n_images))
+        cached = getattr(store, "_graph", None)
+        if cached is not None and cached[0] == key:
+            cached[1].replay()
+            store._replays += 1
+            return cached[2]
+        # the first call runs eagerly (it loads every kernel and sizes every buffer, which a capture must
+        # not do) and then captures the same K iterations for the calls after it; capturing runs nothing
+        out = _iterations(env, agent_k, store, mask, seed, table0)
+        torch.cuda.synchronize(store.device)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            _iterations(env, agent_k, store, mask, seed, table0)
+        store._graph, store._replays = (key, g, out), 0
+        return out
+
+
+def ppo_update(agent, optimizer, store, clip_coef=0.2, vclip=0.2, ent_coef=0.03, vf_coef=0.5, update_epochs=4,
+               minibatch_size=256, target_kl=0.02, max_grad_norm=0.5, generator=None, entropy_bonus=False):
+    """The update of ppo_splendor.py:327-361 over store.minibatches (call store.compute_gae first):
+    clipped policy loss, clipped value loss, the entropy term, grad-norm clip at 0.5 and the target-KL
+    early stop, which like the reference's `break` ends the current epoch only.
+
+    The reference's loss is policy_loss + vf_coef * value_loss + ent_coef * entropy: its double negation
+    (entropy_loss = -entropy; ... + ent_coef * (-entropy_loss)) ADDS the entropy to the minimised loss.
+    That is reproduced by default; entropy_bonus=True subtracts it instead (the usual PPO bonus).
+
+    Returns the last minibatch's policy_loss, value_loss, entropy and approx_kl, first_approx_kl (the
+    first minibatch's, evaluated before any optimiser step) and the number of optimiser steps."""
+    torch = store.torch
+    last, first_kl, steps = None, None, 0
+    sign = -1.0 if entropy_bonus else 1.0
+    for _ in range(int(update_epochs)):
+        for idx in store.minibatches(minibatch_size, generator):
+            mb = store.gather(idx, normalize=True)
+            _, new_logprob, entropy, new_value = agent.get_action_and_value(mb["obs"], mb["mask"], mb["action"])
+            ratio = (new_logprob - mb["logprob"]).exp()
+            clip_adv = torch.clamp(ratio, 1 - clip_coef, 1 + clip_coef) * mb["adv"]
+            policy_loss = -torch.min(ratio * mb["adv"], clip_adv).mean()
+            v_pred = new_value.squeeze(-1)
+            v_clipped = mb["value"] + torch.clamp(v_pred - mb["value"], -vclip, vclip)
+            value_loss = 0.5 * torch.max((v_pred - mb["ret"]).pow(2), (v_clipped - mb["ret"]).pow(2)).mean()
+            entropy = entropy.mean()
+            loss = policy_loss + vf_coef * value_loss + sign * ent_coef * entropy
+            optimizer.zero_grad()
+            loss.backward()
+            torch.nn.utils.clip_grad_norm_(agent.parameters(), max_grad_norm)
+            optimizer.step()
+            steps += 1
+            approx_kl = (mb["logprob"] - new_logprob).mean().detach()
+            if first_kl is None:
+                first_kl = approx_kl
+            last = (policy_loss.detach(), value_loss.detach(), entropy.detach(), approx_kl)
+            if target_kl > 0 and approx_kl.item() > target_kl:
+                break
+    if last is None:
+        raise ValueError("update_epochs must be at least 1")
+    vals = [float(x) for x in last]
+    return {"policy_loss": vals[0], "value_loss": vals[1], "entropy": vals[2], "approx_kl": vals[3],
+            "first_approx_kl": float(first_kl), "optimizer_steps": steps}

@@ -1,0 +1,99 @@
+"""PPO self-play with everything between the env and the optimiser on the device.
+
+    python -m splendor_gym.scripts.ppo_device --num-envs 65536 --num-steps 128 --total-timesteps 100000000
+
+The loop of the reference's ppo_splendor.py with its argument names where they apply: rollouts of
+DualStepVectorEnv against an OpponentPool (current policy with --p-current, else one of --pool-size
+snapshots, drawn per episode), the agent's forward fused (FusedActorCritic), the trajectory in a
+PPORolloutStore, GAE on the device, the update in torch (splendor_gym.ppo).  After each update the
+fused agent and the pool re-pack the new weights; every --snapshot-every-updates updates the pool takes
+a snapshot.  Evaluation, logging to tensorboard and plots are the reference scripts' business
+(splendor_gym.scripts.eval_suite).
+"""
+import argparse
+import time
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser()
+    p.add_argument("--total-timesteps", type=int, default=1_000_000)
+    p.add_argument("--num-envs", type=int, default=4096)
+    p.add_argument("--num-steps", type=int, default=128)
+    p.add_argument("--gamma", type=float, default=0.999)
+    p.add_argument("--gae-lambda", type=float, default=0.95)
+    p.add_argument("--lr", type=float, default=2.5e-4)
+    p.add_argument("--ent-coef", type=float, default=0.03)
+    p.add_argument("--ent-coef-final", type=float, default=0.01)
+    p.add_argument("--vf-coef", type=float, default=0.5)
+    p.add_argument("--clip-coef", type=float, default=0.2)
+    p.add_argument("--vclip", type=float, default=0.2)
+    p.add_argument("--update-epochs", type=int, default=4)
+    p.add_argument("--minibatch-size", type=int, default=256)
+    p.add_argument("--target-kl", type=float, default=0.02)
+    p.add_argument("--lr-anneal", action="store_true")
+    p.add_argument("--seed", type=int, default=42)
+    p.add_argument("--pool-size", type=int, default=12)
+    p.add_argument("--snapshot-every-updates", type=int, default=10)
+    p.add_argument("--p-current", type=float, default=0.25)
+    p.add_argument("--save-path", type=str, default="")
+    p.add_argument("--load-path", type=str, default="", help="a state_dict (.pt) or .safetensors to start from")
+    p.add_argument("--device", type=str, default="cuda:0")
+    p.add_argument("--entropy-bonus", action="store_true",
+                   help="subtract the entropy term (the usual PPO bonus); default: the reference's sign (ppo_update)")
+    p.add_argument("--no-graph", action="store_true", help="run every rollout eagerly instead of replaying a hipGraph")
+    args = p.parse_args(argv)
+
+    import torch
+    from ..fused_policy import FusedActorCritic, OpponentPool
+    from ..policy import ActorCritic
+    from ..ppo import PPORolloutStore, collect, ppo_update
+    from ..selfplay import DualStepVectorEnv
+
+    dev = torch.device(args.device)
+    torch.cuda.set_device(dev)
+    torch.manual_seed(args.seed)
+    agent = ActorCritic().to(dev)
+    if args.load_path.endswith(".safetensors"):
+        from safetensors.torch import load_file
+        agent.load_state_dict(load_file(args.load_path, device=str(dev)))
+    elif args.load_path:
+        agent.load_state_dict(torch.load(args.load_path, map_location=dev))
+    optimizer = torch.optim.Adam(agent.parameters(), lr=args.lr, eps=1e-5)
+    agent_k = FusedActorCritic(agent)
+    pool = OpponentPool(agent, pool_size=args.pool_size, p_current=args.p_current, seed=args.seed)
+    counter = torch.zeros(1, dtype=torch.int64, device=dev)
+    env = DualStepVectorEnv(args.num_envs, device=dev, opponent=pool, opponent_obs=False, step_counter=counter,
+                            agent_obs_u8=True)
+    store = PPORolloutStore(args.num_steps, args.num_envs, dev)
+    gen = torch.Generator(device=dev).manual_seed(args.seed)
+    obs, info = env.reset(seed=args.seed)
+    mask = info["action_mask"]
+    batch = args.num_envs * args.num_steps
+    num_updates = max(1, args.total_timesteps // batch)
+    t0 = time.time()
+    for update in range(num_updates):
+        if args.lr_anneal:
+            optimizer.param_groups[0]["lr"] = args.lr * (1.0 - update / num_updates)
+        obs, mask = collect(env, agent_k, store, obs, mask, seed=args.seed, graph=not args.no_graph)
+        store.compute_gae(gamma=args.gamma, gae_lambda=args.gae_lambda)
+        progress = update / max(1, num_updates - 1)
+        res = ppo_update(agent, optimizer, store, clip_coef=args.clip_coef, vclip=args.vclip,
+                         ent_coef=args.ent_coef + (args.ent_coef_final - args.ent_coef) * progress,
+                         vf_coef=args.vf_coef, update_epochs=args.update_epochs, minibatch_size=args.minibatch_size,
+                         target_kl=args.target_kl, generator=gen, entropy_bonus=args.entropy_bonus)
+        agent_k.refresh()
+        pool.refresh()
+        if (update + 1) % max(1, args.snapshot_every_updates) == 0:
+            pool.add_snapshot()
+        if args.save_path:
+            torch.save(agent.state_dict(), args.save_path)
+        steps = (update + 1) * batch
+        print(f"update {update + 1}/{num_updates} steps {steps} sps {steps / (time.time() - t0):.0f} "
+              f"reward/step {float(store.reward.mean()):+.5f} episodes {int(store.done.sum())} "
+              f"pl {res['policy_loss']:+.4f} vl {res['value_loss']:.4f} ent {res['entropy']:.3f} "
+              f"kl {res['approx_kl']:+.5f} opt-steps {res['optimizer_steps']}", flush=True)
+    env.close()
+
+
+if __name__ == "__main__":
+    main()
