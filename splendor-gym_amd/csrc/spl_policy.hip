@@ -22,20 +22,11 @@
 //     and the Philox-driven inverse-CDF sample are fused after the last tile on register-resident
 //     logits; the sampled action differs from torch's multinomial stream by design (same
 //     distribution), logits match the fp32 module to bf16 accuracy.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <string>
-
-#include "../../include/splendor_amd.h"
-#include "../../include/splendor_policy.h"
-#include "spl_rng.h"
-
-int spl_fail(int code, const std::string &msg);  // spl_engine.hip: sets spl_last_error()
+#include "spl_policy_common.h"
 
 namespace splp {
 
-using spl::philox4x32;
+using namespace splpol;  // PackNet, wave_lds_sync, lds_void, action_uniform
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
@@ -51,9 +42,6 @@ constexpr int kActorChunks = 18, kCriticChunks = 17, kAllChunks = 35;
 #define SPL_ACT_ABL 0
 #endif
 constexpr int ABL_MFMA = 1, ABL_EPI = 2, ABL_XLOAD = 4, ABL_RING = 8;
-#ifndef SPL_ACT_RELOAD_X
-#define SPL_ACT_RELOAD_X 0  // 1: reload the observation after the critic (fewer registers live)
-#endif
 
 constexpr int kWaves = 8, kRowsPerWave = 32, kRowsPerBlock = kWaves * kRowsPerWave;  // 256 tables
 constexpr int kSlots = 6;                         // weight ring: 5 chunks in flight
@@ -73,11 +61,6 @@ constexpr int kCriticTail = 272 * 4;
 // ------------------------------------------------------------------------------------------
 // packing
 // ------------------------------------------------------------------------------------------
-struct PackNet {
-    const float *w1, *b1, *w2, *b2, *w3, *b3;
-    int out;
-};
-
 __device__ __forceinline__ uint16_t bf16_bits(float x) { return __builtin_bit_cast(uint16_t, (__bf16)x); }
 
 // one block per physical chunk
@@ -139,13 +122,6 @@ struct ActArgs {
     int n;
 };
 
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
-    __builtin_amdgcn_wave_barrier();
-}
-
-typedef __attribute__((address_space(3))) void lds_void;
 typedef uint32_t u32x4u __attribute__((ext_vector_type(4), aligned(4)));  // dword-aligned 16-B load
 
 // this wave's 1-KB blocks of one chunk, global -> LDS: wave w moves blocks w, w+8, w+16 (< 20), so
@@ -307,7 +283,9 @@ __global__ __launch_bounds__(512) void k_act(const uint8_t *__restrict__ W, ActA
 #pragma unroll
     for (int c = 0; c < kSlots - 1; ++c) issue_chunk(W, chunk_of(c), ring + c * kChunk, wave, lane);
 
-    // observation B fragments: lane (r, h), k-step s = obs[table r][16s + 8h .. +7] as bf16
+    // observation B fragments: lane (r, h), k-step s = obs[table r][16s + 8h .. +7] as bf16; loaded once
+    // and held through the critic (a second load after the critic, to free its 76 registers during the
+    // critic's layer 2, was a build switch that stayed off; no measurement of it was recorded)
     const int32_t *xrow = a.obs + (size_t)min<int64_t>(tbase + r, (int64_t)a.n - 1) * kObs;
     auto load_x = [&](bf16x8 (&X)[kK1]) {
         if constexpr (SPL_ACT_ABL & ABL_XLOAD) {
@@ -374,11 +352,6 @@ __global__ __launch_bounds__(512) void k_act(const uint8_t *__restrict__ W, ActA
             }
         }
         value += __shfl_xor(value, 32) + a.critic_out[kHid];  // the other lane half's rows, bias
-#if SPL_ACT_RELOAD_X
-        // the observation again (L2 / Infinity Cache) instead of holding its 76 registers through
-        // the critic's layer 2 (the enter() barriers' memory clobbers keep this a real reload)
-        load_x(X);
-#endif
     }
     layer_tanh<kK1>(enter, X, H1, lane);
     layer_tanh<kK2>(enter, H1, H2, lane);
@@ -443,10 +416,7 @@ __global__ __launch_bounds__(512) void k_act(const uint8_t *__restrict__ W, ActA
             }
             const float logS = __logf(S);
             const uint64_t ply = a.ply + (a.ply_base ? *a.ply_base : 0ull);
-            const uint4 rnd = philox4x32(make_uint4((uint32_t)(a.table0 + t), (uint32_t)((uint64_t)(a.table0 + t) >> 32),
-                                                    (uint32_t)ply, (uint32_t)(ply >> 32)),
-                                         make_uint2((uint32_t)a.seed, (uint32_t)(a.seed >> 32) ^ 0xA5C3E1F7u));
-            const float target = (float)(rnd.x >> 8) * (1.f / 16777216.f) * S;
+            const float target = action_uniform(a.seed, ply, a.table0 + t) * S;
             float cum = 0.f;
             int last = 0;
             bool found = false;
@@ -472,13 +442,6 @@ __global__ __launch_bounds__(512) void k_act(const uint8_t *__restrict__ W, ActA
 
 using namespace splp;
 
-int64_t splp32_bytes(int with_critic, int fmt);  // spl_policy32.hip: the fp32 images (fmt 0 exact, 1 two fp16 planes)
-int splp32_pack(const spl_mlp_t *actor, const spl_mlp_t *critic, void *packed, void *stream, int fmt);
-int splp32_act(const uint8_t *img, bool has_critic, bool critic, bool sample, int32_t n, const spl_act_args_t *args,
-               void *stream, int fmt, int groups = 0, int64_t image_stride = 0, const int32_t *group_of = nullptr,
-               void *scratch = nullptr);
-int64_t splp32_group_scratch(int32_t n, int32_t groups);
-
 // the fp32 precisions (spl_policy32.hip): the image format index, or -1
 static int fp32_fmt(int precision) {
     return precision == SPL_PREC_FP32 ? 0 : precision == SPL_PREC_FP32_F16X2 ? 1 : -1;
@@ -500,8 +463,7 @@ int spl_policy_pack(const spl_mlp_t *actor, const spl_mlp_t *critic, int32_t pre
     if (!packed || ((uintptr_t)packed & 255u)) return spl_fail(SPL_E_ARG, "packed image must be 256-byte aligned");
     if (fp32_fmt(precision) >= 0) return splp32_pack(actor, critic, packed, stream, fp32_fmt(precision));
     if (precision != SPL_PREC_BF16) return spl_fail(SPL_E_ARG, "unknown precision");
-    const PackNet A{actor->w1, actor->b1, actor->w2, actor->b2, actor->w3, actor->b3, kAct};
-    const PackNet C = critic ? PackNet{critic->w1, critic->b1, critic->w2, critic->b2, critic->w3, critic->b3, 1} : A;
+    const PackNet A = pack_net(actor, kAct), C = critic ? pack_net(critic, 1) : A;
     const int chunks = critic ? kAllChunks : kActorChunks;
     hipLaunchKernelGGL(k_pack, dim3(chunks), dim3(256), 0, (hipStream_t)stream, A, C, critic ? 1 : 0,
                        static_cast<uint8_t *>(packed));

@@ -32,40 +32,10 @@
 //     networks' layer 1; a hidden layer's output is kPlanes planes x 8 k-steps x 8 elements per lane.
 //   * weights stream once per workgroup through an LDS ring of chunks (one chunk = one 16-row output
 //     tile of one layer, [k-step][plane][lane][8 elements] + biases + row factors; 31 KB for three
-//     bf16 planes in 4 slots, 21 KB for two fp16 planes in 5), global_load_lds, shared by the 8 waves.
+//     bf16 planes, 21 KB for two fp16 planes; four slots either way), LDS-DMA, shared by the 8 waves.
 //   * the critic's one-unit output layer is a per-lane fp32 FMA chain over its layer-2 tiles.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "spl_policy_common.h"
 
-#include <string>
-
-// SPL_P32_PIPE (default 1): each tile's epilogue is issued in stages inside the next tile's k-steps
-// (PendTile below); 0: after its own tile's MFMA chain (round 4's order).  Same results either way.
-#ifndef SPL_P32_PIPE
-#define SPL_P32_PIPE 1
-#endif
-// SPL_P32_RINGV: the weight ring filled through registers (global load, then ds_write a tile later)
-// instead of LDS-DMA (see stage_chunk)
-#ifndef SPL_P32_RINGV
-#define SPL_P32_RINGV 0
-#endif
-// SPL_P32_GROUP 2 (default): one ring barrier per two chunks (four slots: two in use, two loading);
-// exact k_act32<true, true> 215.8 -> 206 us, alternating on one box (profiles/r05/pol_ring_ab_r05g.txt;
-// without any barrier, a racing timing build, 195 us: the barriers cost ~20 us, half of it recovered)
-#ifndef SPL_P32_GROUP
-#define SPL_P32_GROUP 2
-#endif
-// SPL_P32_SPREAD (group-2 ring, pipelined epilogue): the ring's LDS-DMA pieces are issued one per
-// k-step inside the tiles (see tick in act32_body) instead of eight back to back right behind the even
-// barrier (a piece issued among MFMAs costs the wave ~60 cycles of issue, 100-185 in a burst of eight,
-// MI355X_MICROARCH.md).  0: the burst.  Alternating on one box, exact k_act32<true, true>: burst
-// 208.3 us -> one piece per two k-steps of every tile 201.5 (profiles/r05/pol_spread_ab_r05j.txt) ->
-// branch-free pieces 197.1 (pol_nobr_ab_r05k.txt) -> + the paired plane split 198.1 vs 201.4
-// (pol_pair_ab_r05l.txt) -> even tiles load the next pair, hidden chunks without their padding blocks
-// 191.9 vs 198.3 (pol_ahead_ab_r05m.txt)
-#ifndef SPL_P32_SPREAD
-#define SPL_P32_SPREAD 1
-#endif
 // timing ablations (wrong results by design): 1 tanh = identity, 2 one weight chunk (no ring
 // streaming: no LDS-DMA piece after the prologue, no per-tile barrier), 4 A fragments loaded once
 // per tile (no per-group LDS reads), 16 the ring without its barriers (waves race the slots), 32 no
@@ -76,15 +46,9 @@
 #define SPL_POL_ABL 0
 #endif
 
-#include "../../include/splendor_amd.h"
-#include "../../include/splendor_policy.h"
-#include "spl_rng.h"
-
-int spl_fail(int code, const std::string &msg);  // spl_engine.hip: sets spl_last_error()
-
 namespace splp32 {
 
-using spl::philox4x32;
+using namespace splpol;  // PackNet, wave_lds_sync, lds_void, action_uniform
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -100,7 +64,6 @@ struct FmtBf16x3 {  // SPL_PREC_FP32: exact (24 significant bits in three bf16 p
     static constexpr int kPlanes = 3;
     static constexpr int kActScaleExp = 0;  // bf16 has fp32's exponent range: no scaling anywhere
     static constexpr int kRowMaxExp = 0;
-    static constexpr int kSlots = 4;        // ring slots of 31 KB (3 chunks in flight)
     static constexpr bool kExact = true;
 };
 struct FmtF16x2 {   // SPL_PREC_FP32_F16X2: 22 significant bits in two fp16 planes
@@ -110,7 +73,6 @@ struct FmtF16x2 {   // SPL_PREC_FP32_F16X2: 22 significant bits in two fp16 plan
     static constexpr int kPlanes = 2;
     static constexpr int kActScaleExp = 10;  // hidden activations enter the next layer as tanh * 2^10
     static constexpr int kRowMaxExp = 10;    // a weight row's largest |w| is scaled into [2^9, 2^10)
-    static constexpr int kSlots = SPL_P32_GROUP == 2 ? 4 : 5;  // ring slots of 21 KB (4 chunks in flight)
     static constexpr bool kExact = false;
 };
 
@@ -127,6 +89,11 @@ constexpr int kCriticTail = 272 * 4;  // fp32 critic output layer: w3 [256], b3,
 constexpr int kWaves = 8, kRowsPerWave = 16, kRowsPerBlock = kWaves * kRowsPerWave;  // 128 tables
 constexpr int kMaskWave = kRowsPerWave * kAct;  // 720 B
 constexpr int kLogitRow = 49;                   // floats per staged logit row (odd: conflict-free)
+// Weight ring slots, both formats (31 KB / 21 KB each): two in use, two loading, ONE barrier per TWO
+// chunks (the weight ring in act32_body).  Exact k_act32<true, true> 215.8 -> 206 us against a barrier per chunk,
+// alternating on one box (profiles/r05/pol_ring_ab_r05g.txt; without any barrier, a racing timing build,
+// 195 us: the barriers cost ~20 us, half of it recovered).
+constexpr int kSlots = 4;
 
 // sizes that follow from the format
 template <class F>
@@ -138,26 +105,18 @@ struct Geo {
     static constexpr int kChunk = kBiasOff + 1024;
     static constexpr int bias_off(int ks) { return ks * F::kPlanes * kFrag; }
     static constexpr int blocks(int ks) { return ks * F::kPlanes + 1; }
-    static constexpr int kLdsMask = F::kSlots * kChunk;
+    static constexpr int kLdsMask = kSlots * kChunk;
     static constexpr int kLdsCritic = kLdsMask + kWaves * kMaskWave;  // the critic's fp32 output layer (1 KB)
     static constexpr int kLds = kLdsCritic + kCriticTail;
     static constexpr int kChunkBlocks = kChunk / 1024;                           // 31 / 21
     static constexpr int kBlocksPerWave = (kChunkBlocks + kWaves - 1) / kWaves;  // 4 / 3
-    // a wave's loads of the chunks after chunk c that may stay in flight when it enters chunk c
-    static constexpr int kWaitMost = (F::kSlots - 2) * kBlocksPerWave, kWaitLast = (F::kSlots - 2) * (kBlocksPerWave - 1);
     static_assert(kWaves * kRowsPerWave * kLogitRow * 4 <= kLdsMask, "logits reuse the weight ring");
     static_assert(kLds <= 160 * 1024, "LDS");
-    static_assert(kWaitMost <= 63, "vmcnt range");
 };
 
 // chunk order of an image (the order a forward pass consumes them): with a critic
 // [critic L1 x16][critic L2 x16], then [actor L1 x16][actor L2 x16][actor L3 x3]; the actor part of
 // a full image (its last 35 chunks) is laid out exactly as an actor-only image.
-
-struct PackNet {
-    const float *w1, *b1, *w2, *b2, *w3, *b3;
-    int out;
-};
 
 // input unit of lane group g, element e at k-step s: natural order in layer 1 (the observation),
 // the accumulator order of the previous layer's tiles in layers 2-3 (tile 2s + e/4, register e%4)
@@ -308,58 +267,12 @@ __device__ __forceinline__ float tanh_fold(float x, float c) {
 #endif
 }
 
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
-    __builtin_amdgcn_wave_barrier();
-}
-
-typedef __attribute__((address_space(3))) void lds_void;
-
 // the image as a buffer resource: the chunk and block offsets go in the scalar offset, the lane's
 // 16 bytes in a constant VGPR, so an LDS-DMA issue costs no VALU (the 64-bit per-lane address of
 // global_load_lds took a v_lshl_add_u64 per load)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t image_rsrc(const uint8_t *W) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(W), (short)0, 0x7FFFFFF0, 0x00020000);
 }
-// wave w's share of a chunk: 1-KB blocks w, w + 8, w + 16, ... (64 lanes x 16 B each)
-template <class F>
-__device__ __forceinline__ void issue_chunk(__amdgpu_buffer_rsrc_t rs, int chunk, uint8_t *slot, int wave, int lane) {
-    constexpr int kChunk = Geo<F>::kChunk, kBlocks = Geo<F>::kChunkBlocks;
-#pragma unroll
-    for (int i = 0; i < Geo<F>::kBlocksPerWave; ++i) {
-        const int blk = wave + kWaves * i;
-        if (blk < kBlocks)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void *)(slot + blk * 1024), 16, lane * 16,
-                                                     chunk * kChunk + blk * 1024, 0, 0);
-    }
-}
-
-// the VGPR-staged ring (SPL_P32_RINGV): wave w's 1-KB blocks of a chunk as 16-byte buffer loads into
-// registers, then ds_write_b128 into the slot a tile later (an LDS-DMA piece holds the issuing wave's
-// instruction issue ~60-185 cycles, MI355X_MICROARCH.md; a load plus a 16-byte LDS store, ~20)
-template <class F>
-__device__ __forceinline__ void stage_chunk(__amdgpu_buffer_rsrc_t rs, int chunk, u32x4 (&stg)[Geo<F>::kBlocksPerWave],
-                                            int wave, int lane) {
-#pragma unroll
-    for (int i = 0; i < Geo<F>::kBlocksPerWave; ++i) {
-        const int blk = wave + kWaves * i;
-        if (blk < Geo<F>::kChunkBlocks)
-            stg[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, chunk * Geo<F>::kChunk + blk * 1024, 0));
-    }
-}
-template <class F>
-__device__ __forceinline__ void write_chunk(const u32x4 (&stg)[Geo<F>::kBlocksPerWave], uint8_t *slot, int wave, int lane) {
-#pragma unroll
-    for (int i = 0; i < Geo<F>::kBlocksPerWave; ++i) {
-        const int blk = wave + kWaves * i;
-        if (blk < Geo<F>::kChunkBlocks) *reinterpret_cast<u32x4 *>(slot + blk * 1024 + lane * 16) = stg[i];
-    }
-}
-
-// s_waitcnt immediate for vmcnt(n) alone (gfx9: vmcnt[3:0] in bits 3:0, vmcnt[5:4] in 15:14)
-constexpr int vmcnt_imm(int n) { return (n & 15) | ((n >> 4) << 14) | 0x0F70; }
-
 template <class F>
 __device__ __forceinline__ f32x4 mma(const typename F::pelx8 &a, const typename F::pelx8 &b, const f32x4 &c) {
 #if SPL_POL_ABL & 8
@@ -411,8 +324,8 @@ __device__ __forceinline__ bf16x8 obs_residual(const ObsHi &h, int s, int g) {
 // narrow kernel), D k-steps ahead of the MFMAs that use them.
 // kFold: the sum is returned as the products left it (scaled by the row factor's inverse) and
 // `fold` gets the tile's tanh factors (tanh_fold) instead.
-// `stage(s)` runs after k-step s's MFMAs, inside the same scheduling segment (SPL_P32_PIPE: the previous
-// tile's epilogue, one stage per k-step, so its VALU work issues between this tile's MFMAs).
+// `stage(s)` runs after k-step s's MFMAs, inside the same scheduling segment (the previous tile's
+// epilogue, one stage per k-step, so its VALU work issues between this tile's MFMAs: PendTile).
 struct NoStage {
     __device__ __forceinline__ void operator()(int) const {}
 };
@@ -483,14 +396,14 @@ __device__ __forceinline__ uint32_t pk2(typename F::pel lo, typename F::pel hi) 
 
 // the four fp32 outputs h[0..3] of tile t (units 16t + 4g + i), scaled by 2^kActScaleExp (exact) ->
 // elements 4(t & 1) .. +3 of k-step t / 2 of the next layer's B planes
-template <class F, bool kScaled = false>  // kScaled: h already carries 2^kActScaleExp (tanh_fold)
+template <class F>
 __device__ __forceinline__ void put_split(typename F::pelx8 (&H)[F::kPlanes][kKs2], int t, const float (&h)[4]) {
     typedef typename F::pel pel;
     typedef typename F::pelx8 pelx8;
     pel x[4][F::kPlanes];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-        split_planes<F>((F::kActScaleExp && !kScaled) ? h[i] * (float)(1 << F::kActScaleExp) : h[i], x[i]);
+        split_planes<F>(F::kActScaleExp ? h[i] * (float)(1 << F::kActScaleExp) : h[i], x[i]);
 #pragma unroll
     for (int p = 0; p < F::kPlanes; ++p) {
         u32x4 w = __builtin_bit_cast(u32x4, H[p][t >> 1]);
@@ -500,12 +413,14 @@ __device__ __forceinline__ void put_split(typename F::pelx8 (&H)[F::kPlanes][kKs
     }
 }
 
-// ---- the staged epilogue (SPL_P32_PIPE) ------------------------------------------------------------
+// ---- the staged epilogue ---------------------------------------------------------------------------
 // A tile's epilogue (tanh of its four pre-activations per lane, the split of the results into the next
 // layer's B planes, or the critic's value FMAs) is issued in stages inside the NEXT tile's k-step loop:
 // stage s after k-step s's MFMAs, so that its VALU work fills the MFMA pipe's issue gaps instead of
 // following the tile's MFMA chain (where both waves of a SIMD would do VALU at once while the matrix
-// core idles).  Same instructions, same results: a stage only reorders independent work.
+// core idles).  Same instructions, same results: a stage only reorders independent work.  Against the
+// epilogue after each tile's own chain, alternating on one box: exact sample + critic 214 vs 231 us, the
+// fp16-plane kernel unchanged (profiles/r05/pol_pipe_ab_r05d.txt).
 // stages 0-3: tanh of value s; 4-5: the split of values (0, 1) / (2, 3) into the planes of tile t
 template <class F>
 struct PendTile {
@@ -583,34 +498,6 @@ __device__ __forceinline__ void value_stage(PendTile<F> &q, const float *w, floa
     }
 }
 
-// a tile's four pre-activations -> tanh (the format's), scaled for the next layer
-template <class F, int KS, int NB, int D, typename Enter>
-__device__ __forceinline__ void tile_tanh(Enter &enter, const typename F::pelx8 (&B)[NB][KS], int lane, float (&h)[4],
-                                          const ObsHi *hi) {
-    if constexpr (F::kExact) {
-        const f32x4 acc = tile_mma<F, KS, NB, D>(enter(), B, lane, nullptr, hi);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) h[i] = tanh_acc(acc[i]);
-    } else {
-        f32x4 c;
-        const f32x4 acc = tile_mma<F, KS, NB, D, true>(enter(), B, lane, &c);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) h[i] = tanh_fold<F::kActScaleExp>(acc[i], c[i]);
-    }
-}
-
-// a hidden layer: 16 tiles, each tile's tanh split into the next layer's B planes
-template <class F, int KS, int NB, int D, typename Enter>
-__device__ __forceinline__ void layer_tanh(Enter &enter, const typename F::pelx8 (&B)[NB][KS],
-                                           typename F::pelx8 (&H)[F::kPlanes][kKs2], int lane, const ObsHi *hi) {
-#pragma unroll
-    for (int t = 0; t < kTiles; ++t) {
-        float h[4];
-        tile_tanh<F, KS, NB, D>(enter, B, lane, h, hi);
-        put_split<F, true>(H, t, h);
-    }
-}
-
 // the observation's B fragments: lane (r, g), k-step s, element e = obs[table r][32s + 8g + e] from an
 // int32 row, or from a compact row (spl_step_args_t.obs_u8: 300 bytes, move_count >> 8 at byte 297:
 // 8 bytes per k-step as two dword loads, k = 296 alone, k >= 297 zero).  The exact format also returns
@@ -662,11 +549,9 @@ __device__ __forceinline__ uint32_t load_obs(const int32_t *row32, const uint8_t
 
 // A-plane prefetch depth (k-steps) in the ring kernel.  The scheduler places a k-step's LDS reads
 // anywhere inside the previous k-step's segment (often after half its MFMAs), so one k-step ahead left
-// ~3 MFMAs of distance to cover the LDS latency in the hidden layers
-#ifndef SPL_P32_AHEAD2
-#define SPL_P32_AHEAD2 2
-#endif
-constexpr int kAheadL1 = 2, kAheadHid = SPL_P32_AHEAD2;
+// ~3 MFMAs of distance to cover the LDS latency in the hidden layers (1 against 2 in the hidden layers
+// measured no difference: profiles/LOG.md round 5, "A-plane prefetch")
+constexpr int kAheadL1 = 2, kAheadHid = 2;
 
 // The per-table epilogue over one table's 45 logits (`row`) and mask bytes: greedy masked argmax
 // (training_utils.py:263-276) or masked_categorical's sample, log-prob and entropy, plus the critic
@@ -737,10 +622,7 @@ __device__ __forceinline__ void act_epilogue4(const ActArgs &a, const float *row
         T += __shfl_xor(T, 32);
         const float logS = logf(S);
         const uint64_t ply = a.ply + (a.ply_base ? *a.ply_base : 0ull);
-        const uint4 rnd = philox4x32(make_uint4((uint32_t)(a.table0 + t), (uint32_t)((uint64_t)(a.table0 + t) >> 32),
-                                                (uint32_t)ply, (uint32_t)(ply >> 32)),
-                                     make_uint2((uint32_t)a.seed, (uint32_t)(a.seed >> 32) ^ 0xA5C3E1F7u));
-        const float target = (float)(rnd.x >> 8) * (1.f / 16777216.f) * S;
+        const float target = action_uniform(a.seed, ply, a.table0 + t) * S;
         // the scan of group g starts from the groups before it, in order
         const float s0 = __shfl(Sg, r), s1 = __shfl(Sg, r + 16), s2 = __shfl(Sg, r + 32);
         float cum = g == 0 ? 0.f : g == 1 ? s0 : g == 2 ? s0 + s1 : (s0 + s1) + s2;
@@ -767,13 +649,115 @@ __device__ __forceinline__ void act_epilogue4(const ActArgs &a, const float *row
     if (g == 0 && ok) a.action[t] = act;
 }
 
+// ---- named pieces of act32_body ----------------------------------------------------------------------
+// Each compiles to what it compiled to inside the body (profiles/r07/policy_refactor_identity_r07b.txt).
+// k_act32_narrow keeps its own copies of the gathered mask load and of the logits store: out of its
+// body they compile differently there (that wave's lane is threadIdx.x, its logit rows a fixed LDS
+// address, and the compiler uses either only when it sees them in the same function).
+//
+// A wave's mask bytes -> ms[row][action] for its rows [0, valid), in three forms.  Gathered rows (lane
+// i < valid holds row i's table id in tid_own): every byte in one batch of independent loads (a loop
+// reading order[] per byte was two dependent round trips per iteration, ~12 of them).
+__device__ __forceinline__ void mask_gathered(const int8_t *mask, int32_t tid_own, int valid, uint8_t *ms) {
+    const int lane = threadIdx.x & 63;
+    constexpr int kMI = (kMaskWave + 63) / 64;  // 12
+    uint32_t mv[kMI];
+#pragma unroll
+    for (int i = 0; i < kMI; ++i) {
+        const int e = lane + 64 * i, row = e / kAct;
+        const int32_t tt = __shfl(tid_own, row < kRowsPerWave ? row : 0);
+        mv[i] = e < valid * kAct ? (uint32_t)(uint8_t)mask[(int64_t)tt * kAct + e % kAct] : 0u;
+    }
+#pragma unroll
+    for (int i = 0; i < kMI; ++i) {
+        const int e = lane + 64 * i;
+        if (e < valid * kAct) ms[e] = (uint8_t)mv[i];
+    }
+}
+// Consecutive rows starting at msrc: a full wave as dwords, a partial one byte by byte.
+__device__ __forceinline__ void mask_rows(const int8_t *msrc, int valid, int lane, uint8_t *ms) {
+    if (valid == kRowsPerWave) {
+        constexpr int kMQ = kMaskWave / 4;  // 180 dwords
+        for (int q = lane; q < kMQ; q += 64) reinterpret_cast<uint32_t *>(ms)[q] = reinterpret_cast<const uint32_t *>(msrc)[q];
+    } else {
+        for (int e = lane; e < valid * kAct; e += 64) ms[e] = (uint8_t)msrc[e];
+    }
+}
+
+// logits tile t of lane (r, g) (actions 16t + 4g + i) -> table r's staged row of lg
+__device__ __forceinline__ void put_logits(float *lg, int r, int g, int t, const f32x4 &L) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int act = 16 * t + 4 * g + i;
+        if (act < kAct) lg[r * kLogitRow + act] = L[i];
+    }
+}
+
+// the critic's output unit from the lanes' shares of it: the other lane groups' units, then the bias
+__device__ __forceinline__ void value_finish(float &value, const float *bias) {
+    value += __shfl_xor(value, 16);
+    value += __shfl_xor(value, 32);
+    value += *bias;
+}
+
+// tile_mma with the format's fold, its result left pending in q for the next tile's stages
+template <class F, int KS, int NB, int D, class Stage>
+__device__ __forceinline__ void tile_pend(PendTile<F> &q, const uint8_t *slot, const typename F::pelx8 (&B)[NB][KS], int lane,
+                                          const ObsHi *hi, Stage &&stage) {
+    f32x4 cf;
+    const f32x4 acc = tile_mma<F, KS, NB, D, !F::kExact>(slot, B, lane, &cf, hi, stage);
+    q.acc = acc;
+    q.c = cf;
+}
+
+// wave w's share of a whole chunk, back to back (the ring's prologue): 1-KB blocks w, w + 8, w + 16, ...
+// (64 lanes x 16 B each)
+template <class F>
+__device__ __forceinline__ void issue_chunk(__amdgpu_buffer_rsrc_t rs, int chunk, uint8_t *slot, int wave, int lane) {
+    constexpr int kChunk = Geo<F>::kChunk, kBlocks = Geo<F>::kChunkBlocks;
+#pragma unroll
+    for (int i = 0; i < Geo<F>::kBlocksPerWave; ++i) {
+        const int blk = wave + kWaves * i;
+        if (blk < kBlocks)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void *)(slot + blk * 1024), 16, lane * 16,
+                                                     chunk * kChunk + blk * 1024, 0, 0);
+    }
+}
+
 // <false, false> greedy actor, <false, true> sampling actor, <true, true> critic + sampling actor
-// (get_action_and_value), <true, false> critic only (ActorCritic.get_value, ppo_splendor.py:51)
+// (get_action_and_value), <true, false> critic only (ActorCritic.get_value, ppo_splendor.py:51).
+// Every tile but the logits' leaves its result pending (tile_pend) and its epilogue runs as the stages
+// of the next tile, beside the ring's tick: the last tile of a layer inside the next layer's first tile,
+// before that tile's k-step 7 reads the planes it writes.
+//
+// The weight ring (ring, c, dnext, piece, tick, enter in the body): kSlots chunk slots at the start of
+// the LDS, filled by LDS-DMA pieces (1 KB: 64 lanes x 16 B; wave w moves blocks w, w + 8, ... of a chunk)
+// and read by all 8 waves, tile c from slot c % kSlots.  Invariant: behind the barrier of an even tile c,
+// chunks c and c + 1 are complete in their slots and no wave reads the other two slots (they held c - 2
+// and c - 1) before the barrier of c + 2; so tile c loads the next PAIR, chunks c + 2 and c + 3, into
+// them, and every wave waits for its own pieces (vmcnt 0) in front of that next barrier, a tile or more
+// after it issued the last.
+// Measured, each step alternating with the one before it on one box (exact k_act32<true, true>,
+// 65 536 tables; the barrier per two chunks: kSlots):
+//   * the ring filled through registers instead (global loads, ds_write_b128 a tile later): 225-230 us
+//     against ~216, not kept (profiles/r05/pol_ring_ab_r05f.txt);
+//   * ONE LDS-DMA piece per k-step inside the tiles (tick) instead of a wave's eight back to back
+//     behind the barrier (a piece issued among MFMAs costs the wave ~60 cycles of issue, 100-185 in a
+//     burst of eight, MI355X_MICROARCH.md): 208.3 -> 201.5 us (profiles/r05/pol_spread_ab_r05j.txt)
+//     -> branch-free pieces 197.1 (pol_nobr_ab_r05k.txt) -> + the paired plane split 198.1 vs 201.4
+//     (pol_pair_ab_r05l.txt) -> even tiles load the next pair, hidden chunks without their padding
+//     blocks 191.9 vs 198.3 (pol_ahead_ab_r05m.txt).
+// tick(s, ks, odd), after k-step s of the entered tile of ks k-steps: an even tile's share of loading
+// its next pair.  Pieces 0 .. kLast-1 of each chunk (blocks wave + 8 i, which every wave and layer has)
+// one per k-step from k-step 0, branch-free (a branch would end the scheduling region between a k-step's
+// MFMAs and the epilogue stage that should interleave with them; a chunk past the image's last re-loads
+// that last chunk into its free slot); the last piece after the tile's last k-step, where a branch
+// splits nothing, by the waves whose block the chunk's layer has (layer 1: all but the last; a hidden
+// layer: its bias block, wave 0).  Odd tiles load nothing.
 template <class F, bool kCritic, bool kSample>
 __device__ __forceinline__ void act32_body(const uint8_t *__restrict__ W, ActArgs a) {
     typedef typename F::pelx8 pelx8;
     typedef Geo<F> G;
-    constexpr int kSlots = F::kSlots, kChunk = G::kChunk;
     __shared__ __attribute__((aligned(16))) uint8_t lds[G::kLds];
     constexpr bool kActor = kSample || !kCritic;
     constexpr int kTotal = kCritic ? (kActor ? kAllChunks : kCriticChunks) : kActorChunks;
@@ -799,25 +783,62 @@ __device__ __forceinline__ void act32_body(const uint8_t *__restrict__ W, ActArg
     const int valid = (int)max<int64_t>(0, min<int64_t>(kRowsPerWave, rend - tbase));
     // table of row i of this wave (i < valid)
     auto table_of = [&](int i) -> int64_t { return a.order ? (int64_t)a.order[tbase + i] : tbase + i; };
-    uint8_t *ring = lds;
     uint8_t *ms = lds + G::kLdsMask + wave * kMaskWave;
-    const __amdgpu_buffer_rsrc_t wrs = image_rsrc(W);
 
-#if SPL_P32_GROUP == 2
-    static_assert(kSlots == 4, "two chunks per barrier: four slots");
+    // ---- the weight ring (invariant and measurements: above the function)
+    static_assert(kSlots == 4, "one barrier per two chunks: two slots in use, two loading");
+    constexpr int kChunk = G::kChunk;
+    uint8_t *ring = lds;
+    const __amdgpu_buffer_rsrc_t wrs = image_rsrc(W);
     issue_chunk<F>(wrs, 0, ring, wave, lane);
     issue_chunk<F>(wrs, 1, ring + kChunk, wave, lane);
-#elif SPL_P32_RINGV
-    // VGPR-staged ring (SPL_P32_RINGV): chunks 0 .. S-3 by LDS-DMA, chunk S-2 into this wave's staging
-    // registers; enter(c) writes the staged chunk c+S-2 into its slot and loads chunk c+S-1
-    u32x4 stg[G::kBlocksPerWave];
+    int c = 0;      // the next tile's chunk
+    int dnext = 0;  // the first chunk of the pair that the tile entered last loads, if it is even
+    // block blk of chunk ch -> the same block of slot `slot`
+    auto piece = [&](int slot, int ch, int blk) {
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_void *)(ring + slot * kChunk + blk * 1024), 16, lane * 16,
+                                                 ch * kChunk + blk * 1024, 0, 0);
+    };
+    // after k-step s of the entered tile (ks k-steps; s, ks, odd known at compile time): see above
+    auto tick = [&](int s, int ks, int odd) {
+        constexpr int kLast = G::kBlocksPerWave - 1;
+        constexpr bool kNoStream = (SPL_POL_ABL & 2) != 0;  // ablation 2: no streaming at all
+        if (odd || kNoStream) return;
+        if (s < 2 * kLast) {
+            const int j = s / kLast, blk = wave + kWaves * (s % kLast), ch = min(dnext + j, kTotal - 1);
+            piece((dnext + j) % kSlots, ch, blk);
+        }
+        if (s == ks - 1) {
+            const int blk = wave + kWaves * kLast;
 #pragma unroll
-    for (int c = 0; c < kSlots - 2; ++c) issue_chunk<F>(wrs, c, ring + c * kChunk, wave, lane);
-    stage_chunk<F>(wrs, kSlots - 2 < kTotal ? kSlots - 2 : kTotal - 1, stg, wave, lane);
-#else
-#pragma unroll
-    for (int c = 0; c < kSlots - 1; ++c) issue_chunk<F>(wrs, c, ring + c * kChunk, wave, lane);
+            for (int j = 0; j < 2; ++j) {
+                const int ch = dnext + j;
+                const bool l1 = (kCritic && ch >= kCriticChunks ? ch - kCriticChunks : ch) < kTiles;
+                if (ch < kTotal && blk < (l1 ? G::blocks(kKs1) : G::blocks(kKs2))) piece(ch % kSlots, ch, blk);
+            }
+        }
+    };
+    // The next tile's slot.  An even tile first waits for this wave's pieces of chunks c, c + 1 (issued
+    // two tiles ago), then at the barrier for everyone's (and for everyone to be done with c - 2, c - 1);
+    // an odd tile just moves on to the next slot.
+    auto enter = [&]() -> const uint8_t * {
+#if SPL_POL_ABL & 2
+        if (c++ == 0) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+        }
+        return ring;
 #endif
+        if ((c & 1) == 0) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (!(SPL_POL_ABL & 16)) __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+        }
+        const uint8_t *slot = ring + (c % kSlots) * kChunk;
+        dnext = c + 2;
+        ++c;
+        return slot;
+    };
 
     // grouped rows: the wave's table ids, one load (lane i < valid holds row i's), then shuffles
     const int32_t tid_own = (a.order && lane < valid) ? a.order[tbase + lane] : 0;
@@ -835,121 +856,13 @@ __device__ __forceinline__ void act32_body(const uint8_t *__restrict__ W, ActArg
     if constexpr (!kActor) {
         // get_value: no mask
     } else if (a.order) {
-        // gathered rows: every mask byte of the wave's rows in one batch of independent loads (a
-        // loop reading order[] per byte was two dependent round trips per iteration, ~12 of them)
-        constexpr int kMI = (kMaskWave + 63) / 64;  // 12
-        uint32_t mv[kMI];
-#pragma unroll
-        for (int i = 0; i < kMI; ++i) {
-            const int e = lane + 64 * i, row = e / kAct;
-            const int32_t tt = __shfl(tid_own, row < kRowsPerWave ? row : 0);
-            mv[i] = e < valid * kAct ? (uint32_t)(uint8_t)a.mask[(int64_t)tt * kAct + e % kAct] : 0u;
-        }
-#pragma unroll
-        for (int i = 0; i < kMI; ++i) {
-            const int e = lane + 64 * i;
-            if (e < valid * kAct) ms[e] = (uint8_t)mv[i];
-        }
-    } else if (valid == kRowsPerWave) {
-        constexpr int kMQ = kMaskWave / 4;  // 180 dwords
-        const uint32_t *msrc = reinterpret_cast<const uint32_t *>(a.mask + tbase * kAct);
-        for (int q = lane; q < kMQ; q += 64) reinterpret_cast<uint32_t *>(ms)[q] = msrc[q];
+        mask_gathered(a.mask, tid_own, valid, ms);
     } else {
-        const int8_t *msrc = a.mask + tbase * kAct;
-        for (int e = lane; e < valid * kAct; e += 64) ms[e] = (uint8_t)msrc[e];
+        mask_rows(a.mask + tbase * kAct, valid, lane, ms);
     }
-
-    int c = 0;
-#if SPL_P32_SPREAD
-    static_assert(SPL_P32_GROUP == 2 && SPL_P32_PIPE, "spread pieces ride the pipelined k-steps of the group-2 ring");
-    // even tile c loads the next pair, chunks c+2 and c+3 (their slots held c-2 and c-1, free since the
-    // barrier of c), which the barrier of c+2 waits for: a tile or more after the last piece is issued.
-    // Pieces 0 .. kLast-1 of each chunk (blocks wave + 8 i, which every wave and layer has) one per
-    // k-step from k-step 0, branch-free (a branch would end the scheduling region between a k-step's
-    // MFMAs and the epilogue stage that should interleave with them; a chunk past the image's last
-    // re-loads that last chunk into its free slot); the last piece after the tile's last k-step, where
-    // a branch splits nothing, by the waves whose block the chunk's layer has (layer 1: all but the
-    // last; a hidden layer: its bias block, wave 0).  Odd tiles load nothing.
-    int dnext = 0;
-    auto tick = [&](int s, int ks, int odd) {  // after k-step s of a tile of ks k-steps (s, ks, odd known at compile time)
-        constexpr int kLast = G::kBlocksPerWave - 1;
-        constexpr bool kNoStream = (SPL_POL_ABL & 2) != 0;  // ablation 2: no streaming at all
-        if (odd || kNoStream) return;
-        if (s < 2 * kLast) {
-            const int j = s / kLast, blk = wave + kWaves * (s % kLast), ch = min(dnext + j, kTotal - 1);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_void *)(ring + ((dnext + j) % kSlots) * kChunk + blk * 1024),
-                                                     16, lane * 16, ch * kChunk + blk * 1024, 0, 0);
-        }
-        if (s == ks - 1) {
-            const int blk = wave + kWaves * kLast;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int ch = dnext + j;
-                const bool l1 = (kCritic && ch >= kCriticChunks ? ch - kCriticChunks : ch) < kTiles;
-                if (ch < kTotal && blk < (l1 ? G::blocks(kKs1) : G::blocks(kKs2)))
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_void *)(ring + (ch % kSlots) * kChunk + blk * 1024), 16,
-                                                             lane * 16, ch * kChunk + blk * 1024, 0, 0);
-            }
-        }
-    };
-#else
-    auto tick = [&](int, int, int) {};
-#endif
-    auto enter = [&]() -> const uint8_t * {
-#if SPL_POL_ABL & 2
-        if (c++ == 0) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-        }
-        return ring;
-#endif
-#if SPL_P32_GROUP == 2
-        // two chunks per barrier: on even c, wait for this wave's pieces of chunks c, c+1 (issued two tiles
-        // ago), barrier (everyone's landed; everyone is done with c-2, c-1), then issue c+2, c+3 into their
-        // slots; odd c just moves on to the next slot
-        if ((c & 1) == 0) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (!(SPL_POL_ABL & 16)) __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-#if !SPL_P32_SPREAD
-#pragma unroll
-            for (int j = 2; j < 4; ++j)
-                if (c + j < kTotal) issue_chunk<F>(wrs, c + j, ring + ((c + j) % kSlots) * kChunk, wave, lane);
-#endif
-        }
-#elif SPL_P32_RINGV
-        // the staged chunk c+S-2 (loaded one tile ago) -> its slot, which held chunk c-2 (every wave was
-        // done with it at the previous barrier); then, behind this barrier, chunk c is complete (written
-        // S-2 tiles ago, or by the prologue's LDS-DMA) and every wave is done with chunk c-1
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (c + kSlots - 2 < kTotal) write_chunk<F>(stg, ring + ((c + kSlots - 2) % kSlots) * kChunk, wave, lane);
-        __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's part of it is in LDS
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (c + kSlots - 1 < kTotal) stage_chunk<F>(wrs, c + kSlots - 1, stg, wave, lane);
-#else
-        // this wave's part of chunk c landed (later chunks' loads may stay outstanding)
-        if (wave < G::kChunkBlocks - (G::kBlocksPerWave - 1) * kWaves) __builtin_amdgcn_s_waitcnt(vmcnt_imm(G::kWaitMost));
-        else __builtin_amdgcn_s_waitcnt(vmcnt_imm(G::kWaitLast));
-        if (!(SPL_POL_ABL & 16)) __builtin_amdgcn_s_barrier();  // everyone's part landed; slot c-1 is free
-        asm volatile("" ::: "memory");
-        const int nxt = c + kSlots - 1 < kTotal ? c + kSlots - 1 : kTotal - 1;  // past the end: harmless reload
-        issue_chunk<F>(wrs, nxt, ring + ((c + kSlots - 1) % kSlots) * kChunk, wave, lane);
-#endif
-        const uint8_t *slot = ring + (c % kSlots) * kChunk;
-#if SPL_P32_SPREAD
-        dnext = c + 2;
-#endif
-        ++c;
-        return slot;
-    };
 
     pelx8 H1[F::kPlanes][kKs2];
     float value = 0.f;
-#if SPL_P32_PIPE
-    // each tile's epilogue runs in stages inside the next tile's k-steps (PendTile; the last tile of a
-    // layer inside the next layer's first tile, before that tile's k-step 7 reads the planes it writes)
-    constexpr bool kFoldP = !F::kExact;
     PendTile<F> q;
     const float *crit = reinterpret_cast<const float *>(lds + G::kLdsCritic);  // the critic's output layer
     if constexpr (kCritic) {
@@ -957,32 +870,21 @@ __device__ __forceinline__ void act32_body(const uint8_t *__restrict__ W, ActArg
         for (int k = threadIdx.x; k < kCriticTail / 4; k += kWaves * 64) cw[k] = a.critic_out[k];
         // visible to every wave after the first ring barrier (enter)
 #pragma unroll
-        for (int t = 0; t < kTiles; ++t) {  // critic layer 1 -> H1
-            f32x4 cf;
-            const f32x4 acc = tile_mma<F, kKs1, 1, kAheadL1, kFoldP>(enter(), X, lane, &cf, &hi, [&](int s) {
+        for (int t = 0; t < kTiles; ++t)  // critic layer 1 -> H1
+            tile_pend<F, kKs1, 1, kAheadL1>(q, enter(), X, lane, &hi, [&](int s) {
                 tick(s, kKs1, t & 1);
                 if (t > 0) split_stage<F>(H1, t - 1, q, s);
             });
-            q.acc = acc;
-            q.c = cf;
-        }
-        {  // critic layer 2 -> its tiles' shares of the output unit; tile 0 finishes layer 1's last tile
-            f32x4 cf;
-            const f32x4 acc = tile_mma<F, kKs2, F::kPlanes, kAheadHid, kFoldP>(enter(), H1, lane, &cf, nullptr, [&](int s) {
-                tick(s, kKs2, 0);
-                split_stage<F>(H1, kTiles - 1, q, s);
-            });
-            q.acc = acc;
-            q.c = cf;
-        }
+        // critic layer 2 -> its tiles' shares of the output unit; tile 0 finishes layer 1's last tile
+        tile_pend<F, kKs2, F::kPlanes, kAheadHid>(q, enter(), H1, lane, nullptr, [&](int s) {
+            tick(s, kKs2, 0);
+            split_stage<F>(H1, kTiles - 1, q, s);
+        });
         auto crit_l2 = [&](int t, int odd) {
-            f32x4 cf;
-            const f32x4 acc = tile_mma<F, kKs2, F::kPlanes, kAheadHid, kFoldP>(enter(), H1, lane, &cf, nullptr, [&](int s) {
+            tile_pend<F, kKs2, F::kPlanes, kAheadHid>(q, enter(), H1, lane, nullptr, [&](int s) {
                 tick(s, kKs2, odd);
                 value_stage<F>(q, crit + 16 * (t - 1) + 4 * g, value, s);
             });
-            q.acc = acc;
-            q.c = cf;
         };
         crit_l2(1, 1);
 #pragma unroll 1
@@ -994,41 +896,27 @@ __device__ __forceinline__ void act32_body(const uint8_t *__restrict__ W, ActArg
     if constexpr (!kActor) {
 #pragma unroll
         for (int s = 0; s < 4; ++s) value_stage<F>(q, crit + 16 * (kTiles - 1) + 4 * g, value, s);  // the last tile's share
-        value += __shfl_xor(value, 16);  // the other lane groups' units, then the bias
-        value += __shfl_xor(value, 32);
-        value += crit[kHid];
+        value_finish(value, crit + kHid);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the trailing reloads land while the LDS is ours
         if (g == 0 && r < valid) a.value[table_of(r)] = value;
         return;
     }
 #pragma unroll
-    for (int t = 0; t < kTiles; ++t) {  // actor layer 1 -> H1 (the critic's layer 2 has read H1 by now)
-        f32x4 cf;
-        const f32x4 acc = tile_mma<F, kKs1, 1, kAheadL1, kFoldP>(enter(), X, lane, &cf, &hi, [&](int s) {
+    for (int t = 0; t < kTiles; ++t)  // actor layer 1 -> H1 (the critic's layer 2 has read H1 by now)
+        tile_pend<F, kKs1, 1, kAheadL1>(q, enter(), X, lane, &hi, [&](int s) {
             tick(s, kKs1, t & 1);
             if (t > 0) split_stage<F>(H1, t - 1, q, s);
             else if (kCritic) value_stage<F>(q, crit + 16 * (kTiles - 1) + 4 * g, value, s);
         });
-        q.acc = acc;
-        q.c = cf;
-    }
-    if constexpr (kCritic) {
-        value += __shfl_xor(value, 16);
-        value += __shfl_xor(value, 32);
-        value += crit[kHid];
-    }
+    if constexpr (kCritic) value_finish(value, crit + kHid);
     pelx8 H2[F::kPlanes][kKs2];
 #pragma unroll
-    for (int t = 0; t < kTiles; ++t) {  // actor layer 2 -> H2
-        f32x4 cf;
-        const f32x4 acc = tile_mma<F, kKs2, F::kPlanes, kAheadHid, kFoldP>(enter(), H1, lane, &cf, nullptr, [&](int s) {
+    for (int t = 0; t < kTiles; ++t)  // actor layer 2 -> H2
+        tile_pend<F, kKs2, F::kPlanes, kAheadHid>(q, enter(), H1, lane, nullptr, [&](int s) {
             tick(s, kKs2, t & 1);
             if (t == 0) split_stage<F>(H1, kTiles - 1, q, s);
             else split_stage<F>(H2, t - 1, q, s);
         });
-        q.acc = acc;
-        q.c = cf;
-    }
     f32x4 L[kActTiles];
 #pragma unroll
     for (int t = 0; t < kActTiles; ++t)  // the logits (true scale)
@@ -1036,57 +924,13 @@ __device__ __forceinline__ void act32_body(const uint8_t *__restrict__ W, ActArg
             tick(s, kKs2, t & 1);
             if (t == 0) split_stage<F>(H2, kTiles - 1, q, s);
         });
-#else
-    if constexpr (kCritic) {
-        layer_tanh<F, kKs1, 1, kAheadL1>(enter, X, H1, lane, &hi);
-        // layer 2 tile t -> tanh -> its units' share of the fp32 output unit, on the spot
-#pragma unroll 1
-        for (int t = 0; t < kTiles; ++t) {
-            const float4 w = *reinterpret_cast<const float4 *>(a.critic_out + 16 * t + 4 * g);
-            float h[4];
-            if constexpr (F::kExact) {
-                const f32x4 acc = tile_mma<F, kKs2, F::kPlanes, kAheadHid>(enter(), H1, lane);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) h[i] = tanh_acc(acc[i]);
-            } else {
-                f32x4 cf;
-                const f32x4 acc = tile_mma<F, kKs2, F::kPlanes, kAheadHid, true>(enter(), H1, lane, &cf);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) h[i] = tanh_fold<0>(acc[i], cf[i]);
-            }
-            value = __builtin_fmaf(w.x, h[0], value);
-            value = __builtin_fmaf(w.y, h[1], value);
-            value = __builtin_fmaf(w.z, h[2], value);
-            value = __builtin_fmaf(w.w, h[3], value);
-        }
-        value += __shfl_xor(value, 16);  // the other lane groups' units, then the bias
-        value += __shfl_xor(value, 32);
-        value += a.critic_out[kHid];
-    }
-    if constexpr (!kActor) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the trailing reloads land while the LDS is ours
-        if (g == 0 && r < valid) a.value[table_of(r)] = value;
-        return;
-    }
-    layer_tanh<F, kKs1, 1, kAheadL1>(enter, X, H1, lane, &hi);
-    pelx8 H2[F::kPlanes][kKs2];
-    layer_tanh<F, kKs2, F::kPlanes, kAheadHid>(enter, H1, H2, lane, nullptr);
-    f32x4 L[kActTiles];
-#pragma unroll
-    for (int t = 0; t < kActTiles; ++t) L[t] = tile_mma<F, kKs2, F::kPlanes, kAheadHid>(enter(), H2, lane);
-#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the trailing reloads
     __builtin_amdgcn_s_barrier();                      // every wave is done with the ring
 
     // logits -> LDS [table][action] (reusing the ring), then the per-table epilogue
     float *lg = reinterpret_cast<float *>(ring) + wave * kRowsPerWave * kLogitRow;
 #pragma unroll
-    for (int t = 0; t < kActTiles; ++t)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int act = 16 * t + 4 * g + i;
-            if (act < kAct) lg[r * kLogitRow + act] = L[t][i];
-        }
+    for (int t = 0; t < kActTiles; ++t) put_logits(lg, r, g, t, L[t]);
     wave_lds_sync();
     if (a.logits) {
         for (int i = lane; i < valid * kAct; i += 64)
@@ -1185,7 +1029,7 @@ __device__ __forceinline__ void act32_narrow_body(const uint8_t *__restrict__ Wb
     pelx8 X[1][kKs1];
     ObsHi hi{0u, a.obs_u8 ? nullptr : a.obs + (size_t)xt * kObs, a.obs_u8 ? a.obs_u8 + (size_t)xt * 300 : nullptr};
     hi.mask = load_obs<F>(hi.row32, hi.row8, g, X);
-    if (wave == 0) {  // the wave-tile's mask bytes (gathered rows), for the epilogue
+    if (wave == 0) {  // the wave-tile's mask bytes (gathered rows), for the epilogue: mask_gathered, inline here
         constexpr int kMI = (kMaskWave + 63) / 64;
         uint32_t mv[kMI];
 #pragma unroll
@@ -1256,8 +1100,7 @@ int64_t splp32_bytes(int with_critic, int fmt) {
 }
 
 int splp32_pack(const spl_mlp_t *actor, const spl_mlp_t *critic, void *packed, void *stream, int fmt) {
-    const PackNet A{actor->w1, actor->b1, actor->w2, actor->b2, actor->w3, actor->b3, kAct};
-    const PackNet C = critic ? PackNet{critic->w1, critic->b1, critic->w2, critic->b2, critic->w3, critic->b3, 1} : A;
+    const PackNet A = pack_net(actor, kAct), C = critic ? pack_net(critic, 1) : A;
     if (fmt)
         hipLaunchKernelGGL(k_pack32h, dim3(critic ? kAllChunks : kActorChunks), dim3(256), 0, (hipStream_t)stream, A, C,
                            critic ? 1 : 0, static_cast<uint8_t *>(packed));
@@ -1377,11 +1220,8 @@ struct HalfK {
     static constexpr auto fn = k_act32h<C, S>;
 };
 
-// image: a packed fp32 image of format `fmt` (full when has_critic); critic: evaluate the critic
-// (SAMPLE with value)
 int splp32_act(const uint8_t *img, bool has_critic, bool critic, bool sample, int32_t n, const spl_act_args_t *args,
-               void *stream, int fmt, int groups = 0, int64_t image_stride = 0, const int32_t *group_of = nullptr,
-               void *scratch = nullptr) {
+               void *stream, int fmt, int groups, int64_t image_stride, const int32_t *group_of, void *scratch) {
     const int64_t chunk = fmt ? Geo<FmtF16x2>::kChunk : Geo<FmtBf16x3>::kChunk;
     const float *critic_out = has_critic ? reinterpret_cast<const float *>(img + (size_t)kAllChunks * chunk) : nullptr;
     ActArgs a{args->obs,    args->obs_u8, args->mask,     args->action, args->logprob, args->entropy, args->value,

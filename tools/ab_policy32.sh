@@ -2,25 +2,29 @@
 # A/B of k_act32 build variants (spl_policy32.hip), alternating on one box:
 #   BUILD=1 tools/ab_policy32.sh            # here: the variants below into splendor-gym_amd/ablate/
 #   tools/ab_policy32.sh [rounds]           # GPU box: tools/bench_policy.py per variant, `rounds` passes
-# Variants: name:REV:FLAGS (REV = a git revision of the sources, or "wt" for the working tree).
+# Variants: name:REV:FLAGS (REV = a git revision of the sources, or "wt" for the working tree; FLAGS, comma
+# separated, are added to the product's).  Every source is compiled with the flags csrc/Makefile gives it.
 set -o pipefail
 D=splendor-gym_amd/ablate
+C=splendor-gym_amd/csrc
 VARIANTS=${VARIANTS:-"head:HEAD: wt:wt:"}
-F="-O3 -std=c++17 -fPIC --offload-arch=gfx950"
+flags_of() { make -s -C $C flags-$1; }
 if [ "${BUILD:-0}" = "1" ]; then
   mkdir -p $D/obj
-  for s in spl_engine spl_policy spl_dual; do
-    [ $D/obj/$s.o -nt splendor-gym_amd/csrc/$s.hip ] || /opt/rocm/bin/hipcc $F -c -o $D/obj/$s.o splendor-gym_amd/csrc/$s.hip || exit 1
+  others=""
+  for s in $(make -s -C $C names); do
+    [ $s = spl_policy32 ] && continue
+    others="$others $D/obj/$s.o"
+    [ $D/obj/$s.o -nt $C/$s.hip ] || /opt/rocm/bin/hipcc $(flags_of $s) -c -o $D/obj/$s.o $C/$s.hip || exit 1
   done
   for v in $VARIANTS; do
-    IFS=: read -r name rev flags <<< "$v"
-    src=splendor-gym_amd/csrc/spl_policy32.hip
+    IFS=: read -r name rev extra <<< "$v"
+    src=$C/spl_policy32.hip
     if [ "$rev" != "wt" ]; then
-      t=$(mktemp -d); git archive "$rev" splendor-gym_amd/csrc include | tar -x -C $t; src=$t/splendor-gym_amd/csrc/spl_policy32.hip
+      t=$(mktemp -d); git archive "$rev" $C include | tar -x -C $t; src=$t/$C/spl_policy32.hip
     fi
-    /opt/rocm/bin/hipcc $F ${flags//,/ } -c -o $D/obj/p32v_$name.o $src || exit 1
-    /opt/rocm/bin/hipcc $F -shared -o $D/libp32v_$name.so $D/obj/spl_engine.o $D/obj/spl_policy.o $D/obj/spl_dual.o \
-      $D/obj/p32v_$name.o || exit 1
+    /opt/rocm/bin/hipcc $(flags_of spl_policy32) ${extra//,/ } -c -o $D/obj/p32v_$name.o $src || exit 1
+    /opt/rocm/bin/hipcc $(flags_of spl_engine) -shared -o $D/libp32v_$name.so $others $D/obj/p32v_$name.o || exit 1
   done
   exit 0
 fi

@@ -5,11 +5,18 @@ set -o pipefail
 D=splendor-gym_amd/ablate
 C=splendor-gym_amd/csrc
 VARIANTS="full:0 no_mfma:1 no_epi:2 no_xload:4 no_ring:8 only_ring:7 only_mfma:14"
+flags_of() { make -s -C $C flags-$1; }  # the flags csrc/Makefile compiles that source with
 if [ "${BUILD:-0}" = "1" ]; then
-  mkdir -p $D
+  mkdir -p $D/obj
+  others=""
+  for s in $(make -s -C $C names); do
+    [ $s = spl_policy ] && continue
+    others="$others $D/obj/$s.o"
+    [ $D/obj/$s.o -nt $C/$s.hip ] || /opt/rocm/bin/hipcc $(flags_of $s) -c -o $D/obj/$s.o $C/$s.hip || exit 1
+  done
   for v in $VARIANTS; do
-    /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -DSPL_ACT_ABL=${v#*:} -shared \
-      -o $D/libpol_${v%%:*}.so $C/spl_engine.hip $C/spl_policy.hip $C/spl_dual.hip || exit 1
+    /opt/rocm/bin/hipcc $(flags_of spl_policy) -DSPL_ACT_ABL=${v#*:} -c -o $D/obj/pol_${v%%:*}.o $C/spl_policy.hip || exit 1
+    /opt/rocm/bin/hipcc $(flags_of spl_engine) -shared -o $D/libpol_${v%%:*}.so $others $D/obj/pol_${v%%:*}.o || exit 1
   done
   exit 0
 fi

@@ -7,17 +7,19 @@ set -o pipefail
 D=splendor-gym_amd/ablate
 C=splendor-gym_amd/csrc
 VARIANTS=${VARIANTS:-"full:0 notanh:1 noring:2 noafrd:4 noring_notanh:3 mfma_only:7"}
-F="-O3 -std=c++17 -fPIC --offload-arch=gfx950"
+flags_of() { make -s -C $C flags-$1; }  # the flags csrc/Makefile compiles that source with
 if [ "${BUILD:-0}" = "1" ]; then
   mkdir -p $D/obj
-  for s in spl_engine spl_policy spl_dual; do
+  others=""
+  for s in $(make -s -C $C names); do
+    [ $s = spl_policy32 ] && continue
+    others="$others $D/obj/$s.o"
     if [ $C/obj/$s.o -nt $C/$s.hip ]; then cp $C/obj/$s.o $D/obj/$s.o; fi  # the product build's objects (csrc/Makefile)
-    [ $D/obj/$s.o -nt $C/$s.hip ] || /opt/rocm/bin/hipcc $F -c -o $D/obj/$s.o $C/$s.hip || exit 1
+    [ $D/obj/$s.o -nt $C/$s.hip ] || /opt/rocm/bin/hipcc $(flags_of $s) -c -o $D/obj/$s.o $C/$s.hip || exit 1
   done
   for v in $VARIANTS; do
-    /opt/rocm/bin/hipcc $F -DSPL_POL_ABL=${v#*:} -c -o $D/obj/p32_${v%%:*}.o $C/spl_policy32.hip || exit 1
-    /opt/rocm/bin/hipcc $F -shared -o $D/libp32_${v%%:*}.so $D/obj/spl_engine.o $D/obj/spl_policy.o \
-      $D/obj/spl_dual.o $D/obj/p32_${v%%:*}.o || exit 1
+    /opt/rocm/bin/hipcc $(flags_of spl_policy32) -DSPL_POL_ABL=${v#*:} -c -o $D/obj/p32_${v%%:*}.o $C/spl_policy32.hip || exit 1
+    /opt/rocm/bin/hipcc $(flags_of spl_engine) -shared -o $D/libp32_${v%%:*}.so $others $D/obj/p32_${v%%:*}.o || exit 1
   done
   exit 0
 fi

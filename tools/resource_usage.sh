@@ -1,9 +1,10 @@
-# Per-kernel register / LDS / scratch usage of the gfx950 build (hipcc -Rpass-analysis=kernel-resource-usage)
+# Per-kernel register / LDS / scratch usage of the gfx950 build (hipcc -Rpass-analysis=kernel-resource-usage):
+# every source of csrc/Makefile, each with the flags the Makefile compiles it with
 set -o pipefail
 D=$(cd "$(dirname "$0")/.." && pwd)/splendor-gym_amd/csrc
-for f in spl_engine.hip spl_policy.hip spl_policy32.hip spl_dual.hip; do
-  /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 --cuda-device-only -c -Rpass-analysis=kernel-resource-usage \
-      -o /dev/null "$D/$f" 2>&1
+for n in $(make -s -C "$D" names); do
+  /opt/rocm/bin/hipcc $(make -s -C "$D" flags-$n) --cuda-device-only -c -Rpass-analysis=kernel-resource-usage \
+      -o /dev/null "$D/$n.hip" 2>&1
 done | python3 -c '
 import re, sys, subprocess
 rows, cur = [], None
