@@ -104,6 +104,35 @@ class PpoGather(ctypes.Structure):
                                         "out_ret", "errors")]
 
 
+EVAL_ABI = 1                       # SPL_EVAL_ABI (include/splendor_eval.h)
+POLICY_GREEDY_V2, EVAL_KEEP = 3, -1  # SPL_POLICY_GREEDY_V2, SPL_EVAL_KEEP: spl_eval_scripted_act only
+EVAL_COLS = 8                      # wins, losses, draws, unfinished, sum turns, sum prestige, checks, illegal
+
+
+class EvalAct(ctypes.Structure):
+    """spl_eval_act_t (include/splendor_eval.h)"""
+    _fields_ = [(k, c_void_p) for k in ("mask", "obs", "obs_u8", "policy_of", "table_key", "ply_base", "action",
+                                        "errors")] + \
+               [("seed", c_uint64), ("ply", c_uint64), ("table0", c_int64), ("policy", c_int32), ("reserved", c_int32)]
+
+
+class EvalCheck(ctypes.Structure):
+    """spl_eval_check_t (include/splendor_eval.h)"""
+    _fields_ = [(k, c_void_p) for k in ("action", "mask", "playing", "checks", "illegal")]
+
+
+class EvalTally(ctypes.Structure):
+    """spl_eval_tally_t (include/splendor_eval.h)"""
+    _fields_ = [(k, c_void_p) for k in ("done", "game_ended_on", "agent_step_reward", "opp_reward", "final_obs",
+                                        "playing", "result", "turns", "prestige")]
+
+
+class EvalReduce(ctypes.Structure):
+    """spl_eval_reduce_t (include/splendor_eval.h)"""
+    _fields_ = [(k, c_void_p) for k in ("group_of", "playing", "result", "turns", "prestige", "checks", "illegal",
+                                        "out")]
+
+
 # spl_table_t (include/splendor_table.h) as a numpy structured dtype
 PLAYER_DTYPE = np.dtype([("tokens", "<i4", 6), ("bonuses", "<i4", 5), ("prestige", "<i4"),
                          ("n_reserved", "<i4"), ("reserved", "<i4", 3), ("revealed", "<i4", 3),
@@ -173,6 +202,12 @@ SIGNATURES = {
     "spl_ppo_gae_scratch_bytes": ([c_int32], c_int64),
     "spl_ppo_gae": ([c_int32, c_int32, ctypes.POINTER(PpoGae), c_void_p], c_int32),
     "spl_ppo_gather": ([c_int32, ctypes.POINTER(PpoGather), c_void_p], c_int32),
+    # include/splendor_eval.h
+    "spl_eval_abi_version": ([], c_int32),
+    "spl_eval_scripted_act": ([c_int32, ctypes.POINTER(EvalAct), c_void_p], c_int32),
+    "spl_eval_check": ([c_int32, ctypes.POINTER(EvalCheck), c_void_p], c_int32),
+    "spl_eval_tally": ([c_int32, ctypes.POINTER(EvalTally), c_void_p], c_int32),
+    "spl_eval_reduce": ([c_int32, c_int32, ctypes.POINTER(EvalReduce), c_void_p], c_int32),
 }
 
 

@@ -7,8 +7,10 @@ DualStepVectorEnv against an OpponentPool (current policy with --p-current, else
 snapshots, drawn per episode), the agent's forward fused (FusedActorCritic), the trajectory in a
 PPORolloutStore, GAE on the device, the update in torch (splendor_gym.ppo).  After each update the
 fused agent and the pool re-pack the new weights; every --snapshot-every-updates updates the pool takes
-a snapshot.  Evaluation, logging to tensorboard and plots are the reference scripts' business
-(splendor_gym.scripts.eval_suite).
+a snapshot.  --eval-every-updates N evaluates before training and every N updates, --eval-games games
+against each of random, greedy_v1, basic, the agent itself and greedy_v2 in one batch on the device
+(splendor_gym.evaluation.DeviceEvaluator), one line per opponent.  Logging to tensorboard and plots are
+the reference scripts' business.
 """
 import argparse
 import time
@@ -41,6 +43,9 @@ def main(argv=None):
     p.add_argument("--entropy-bonus", action="store_true",
                    help="subtract the entropy term (the usual PPO bonus); default: the reference's sign (ppo_update)")
     p.add_argument("--no-graph", action="store_true", help="run every rollout eagerly instead of replaying a hipGraph")
+    p.add_argument("--eval-every-updates", type=int, default=0,
+                   help="evaluate before training and every N updates (0: never), as ppo_splendor.py does")
+    p.add_argument("--eval-games", type=int, default=400, help="games per opponent kind of one evaluation")
     args = p.parse_args(argv)
 
     import torch
@@ -70,6 +75,22 @@ def main(argv=None):
     mask = info["action_mask"]
     batch = args.num_envs * args.num_steps
     num_updates = max(1, args.total_timesteps // batch)
+    evaluator = None
+    if args.eval_every_updates > 0:
+        from ..evaluation import DeviceEvaluator
+        # run_evaluation_suite's opponents in its order (group g plays seed + g), greedy_v2 after them
+        evaluator = DeviceEvaluator(args.eval_games, opponents=("random", "greedy_v1", "basic", "self_play", "greedy_v2"),
+                                    device=dev, policy_seed=args.seed, graph=not args.no_graph)
+
+    def evaluate(update_seed, steps):
+        print(f"evaluation at step {steps} ({args.eval_games} games per opponent)", flush=True)
+        for name, r in evaluator.run(agent_k, seed=update_seed).items():
+            print(f"  eval vs {name}: win_rate {r['win_rate']:.3f} +- {r['win_rate_ci95']:.3f} "
+                  f"avg_turns {r['avg_turns']:.1f} avg_prestige {r['avg_prestige']:.2f} "
+                  f"illegal_action_rate {r['illegal_action_rate']:.4f}", flush=True)
+
+    if evaluator is not None:
+        evaluate(0, 0)  # ppo_splendor.py:195-197
     t0 = time.time()
     for update in range(num_updates):
         if args.lr_anneal:
@@ -92,6 +113,10 @@ def main(argv=None):
               f"reward/step {float(store.reward.mean()):+.5f} episodes {int(store.done.sum())} "
               f"pl {res['policy_loss']:+.4f} vl {res['value_loss']:.4f} ent {res['entropy']:.3f} "
               f"kl {res['approx_kl']:+.5f} opt-steps {res['optimizer_steps']}", flush=True)
+        if evaluator is not None and (update + 1) % args.eval_every_updates == 0:
+            evaluate(update, steps)  # ppo_splendor.py:382-388, on the refreshed agent_k
+    if evaluator is not None:
+        evaluator.close()
     env.close()
 
 

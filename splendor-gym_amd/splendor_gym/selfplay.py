@@ -8,6 +8,8 @@ opponent move) with the opponent's actions computed in between on the device, by
 
   * a device policy fused into the agent-move kernel: "random" (wrappers/selfplay.py:66-73),
     "greedy_v1" / "basic_priority" (scripts/eval_suite.py:9-78; random choices are Philox draws),
+  * "greedy_v2" (eval_suite.py:80-128, bank-aware): the scripted kernel of include/splendor_eval.h between
+    the two launches (opponents.ScriptedOpponents, which also mixes opponent kinds per table),
   * or any batched callable (obs int32 [N,297], mask int8 [N,45]) -> actions [N], e.g.
     splendor_gym.policy.greedy_opponent_from(actor) for self-play against a network
     (eval_suite.py:131-141 model_greedy_policy_from),
@@ -41,9 +43,11 @@ import torch
 
 from . import _native
 from .device import Engine
+from .opponents import ScriptedOpponents
 
 _DEVICE_POLICIES = {"random": _native.POLICY_UNIFORM, "greedy_v1": _native.POLICY_GREEDY_V1,
                     "basic_priority": _native.POLICY_BASIC_PRIORITY}
+_SCRIPTED_CALLABLES = ("greedy_v2",)  # names served by opponents.ScriptedOpponents (spl_eval_scripted_act)
 
 
 class DualInfo(Mapping):
@@ -85,8 +89,9 @@ class DualStepVectorEnv:
         agent_obs_u8: keep `self.agent_obs_u8`, uint8 [n, 300], the compact rows (spl_step_args_t.obs_u8)
         of the agent's observation, written by the opponent's step beside the int32 obs it returns
         (ABI 8): a fused actor reads a quarter of the bytes (FusedActorCritic.act accepts them)."""
-        if isinstance(opponent, str) and opponent not in _DEVICE_POLICIES:
-            raise ValueError(f"unknown device opponent {opponent!r}; choose {sorted(_DEVICE_POLICIES)} or a callable")
+        if isinstance(opponent, str) and opponent not in _DEVICE_POLICIES and opponent not in _SCRIPTED_CALLABLES:
+            raise ValueError(f"unknown device opponent {opponent!r}; choose "
+                             f"{sorted(_DEVICE_POLICIES) + list(_SCRIPTED_CALLABLES)} or a callable")
         if step_counter is not None and not (step_counter.dtype == torch.int64 and step_counter.numel() == 1):
             raise ValueError("step_counter must be an int64 [1] tensor on the env's device")
         self.eng = Engine(num_envs, 2, device=device, refill_period=refill_period, table0=table0)
@@ -94,6 +99,13 @@ class DualStepVectorEnv:
         if step_counter is not None and step_counter.device != self.device:
             self.eng.close()
             raise ValueError("step_counter must be an int64 [1] tensor on the env's device")
+        scripted_by_name = isinstance(opponent, str) and opponent in _SCRIPTED_CALLABLES
+        if scripted_by_name:
+            # no fused form in the step kernel: the scripted kernel between the two phases, through the
+            # callable path; its ply is 1 + the env's device step counter, so it advances on the device
+            if step_counter is None:
+                step_counter = torch.zeros(1, dtype=torch.int64, device=self.device)
+            opponent = ScriptedOpponents(name=opponent, seed=policy_seed, ply_base=step_counter, table0=table0)
         self.opponent = opponent
         self.policy_seed = int(policy_seed)
         self.want_opp_obs = opponent_obs
@@ -101,6 +113,8 @@ class DualStepVectorEnv:
         n, dev = num_envs, self.device
         z = lambda dt: t.zeros(n, dtype=dt, device=dev)
         self.opp_actions = z(t.int32)
+        if scripted_by_name:  # the env's own callable writes the env's own buffer
+            opponent.out = self.opp_actions
         # phase A (agent move) small outputs, kept apart from the engine's (phase B) buffers
         self.small_a = (z(t.float32), z(t.uint8), z(t.uint8), z(t.int8))
         self.agent_reward, self.opp_reward = z(t.float32), z(t.float32)
