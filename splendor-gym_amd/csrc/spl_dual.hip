@@ -1,16 +1,9 @@
 // spl_dual.hip — glue of the batched dual step (include/splendor_dual.h): the per-table branches
 // of wrappers/dual_step_native.py:90-193 as two elementwise kernels, so a dual step is four or
 // five launches instead of a chain of ~30 tensor ops.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <string>
-
-#include "../../include/splendor_amd.h"
 #include "../../include/splendor_dual.h"
+#include "spl_common.h"
 #include "spl_rng.h"
-
-int spl_fail(int code, const std::string &msg);  // spl_engine.hip
 
 namespace spld {
 
@@ -132,8 +125,7 @@ int spl_dual_gate(int32_t n, const uint8_t *terminated_a, const uint8_t *flags_a
     if (!terminated_a || !flags_a || !opp_action) return spl_fail(SPL_E_ARG, "null buffer");
     hipLaunchKernelGGL(k_dual_gate, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, terminated_a, flags_a,
                        opp_action);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SPL_OK : spl_fail(SPL_E_HIP, std::string("k_dual_gate: ") + hipGetErrorString(e));
+    return spl_launched("k_dual_gate");
 }
 
 static int dual_finish(int32_t n, const spl_dual_io_t *io, const spl_dual_draw_t *draw, void *stream) {
@@ -165,8 +157,7 @@ static int dual_finish(int32_t n, const spl_dual_io_t *io, const spl_dual_draw_t
                            io->terminated_b, reinterpret_cast<const int4 *>(io->obs),
                            reinterpret_cast<const int4 *>(io->final_obs), reinterpret_cast<int4 *>(io->opp_obs));
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SPL_OK : spl_fail(SPL_E_HIP, std::string("k_dual_finish: ") + hipGetErrorString(e));
+    return spl_launched("k_dual_finish");
 }
 
 int spl_dual_finish(int32_t n, const spl_dual_io_t *io, void *stream) { return dual_finish(n, io, nullptr, stream); }
@@ -184,8 +175,7 @@ int spl_dual_draw_opponents(int32_t n, const uint8_t *draw, uint32_t *episode, i
     if (!(p_current >= 0.f && p_current <= 1.f)) return spl_fail(SPL_E_ARG, "p_current must be in [0, 1]");
     hipLaunchKernelGGL(k_draw_opponents, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, draw, episode,
                        group_of, pool_slots, pool_len, p_current, seed, table0);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SPL_OK : spl_fail(SPL_E_HIP, std::string("k_draw_opponents: ") + hipGetErrorString(e));
+    return spl_launched("k_draw_opponents");
 }
 
 }  // extern "C"

@@ -25,8 +25,10 @@
 #include <vector>
 
 #include "../../include/splendor_amd.h"
+#include "spl_common.h"
 #include "spl_layout.h"
 #include "spl_rng.h"
+#include "spl_scripted.h"
 
 namespace spl {
 
@@ -76,9 +78,6 @@ struct KStep {
     int autoreset;
     int policy;
 };
-
-constexpr int kObsDim = 297;
-constexpr int kObsU8 = 300;  // compact observation row (spl_step_args_t.obs_u8): 297 bytes + move_count >> 8 + 2 zero
 
 // Ablation switches for profiling builds only (tools/ablate.py); the product build defines none.
 #ifndef SPL_ABL
@@ -290,15 +289,6 @@ __device__ __forceinline__ uint32_t bget(uint32_t w, int k) { return (w >> (8 * 
 __device__ __forceinline__ uint32_t bset(uint32_t w, int k, uint32_t v) {
     return (w & ~(0xFFu << (8 * k))) | ((v & 0xFFu) << (8 * k));
 }
-// Cross-lane LDS hand-off inside ONE wave (every workgroup here is a single wave).
-// __syncthreads() would also emit s_waitcnt vmcnt(0): the wave would stall until its pending
-// global stores drain behind every other wave's observation traffic.  LDS executes one wave's
-// operations in order, so ordering the compiler (wavefront fence) and the LDS counter suffices.
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0) only
-    __builtin_amdgcn_wave_barrier();
-}
 
 // Launder a value through an empty asm so that a select chain over struct members stays a
 // select of VALUES: otherwise LLVM folds "c ? s.a : s.b" into a load at a selected offset,
@@ -440,12 +430,6 @@ __device__ __forceinline__ bool afford(const Have &h, uint4 rec) {
     const int need = (int)(s & 0xFFFFu) + (int)(s >> 16) + max((int)bget(rec.w, 0) - (int)h.k, 0);
     return h.gold >= need;
 }
-
-// take-3 colour sets in itertools.combinations(range(5), 3) order (engine/encode.py:35)
-constexpr uint64_t kTake3Masks = (0x07ull) | (0x0Bull << 5) | (0x13ull << 10) | (0x0Dull << 15) |
-                                 (0x15ull << 20) | (0x19ull << 25) | (0x0Eull << 30) | (0x16ull << 35) |
-                                 (0x1Aull << 40) | (0x1Cull << 45);
-__device__ __forceinline__ uint32_t take3_mask(int i) { return (uint32_t)(kTake3Masks >> (5 * i)) & 31u; }
 
 // engine/rules.py:40-93 legal_moves -> 45-bit mask
 __device__ __forceinline__ uint64_t legal_mask(const uint32_t *sw, const Pl &p, const int bank[6], const Consts &L) {
@@ -1531,76 +1515,14 @@ __device__ __forceinline__ uint64_t legal_of(const Tab<P> &T, const Consts &L) {
     return legal_mask(T.sw, p, bank, L);
 }
 
-// the uniform policy's Philox(seed; table, ply) word: independent of the state, so a wave with spare
-// time can draw it ahead (the dealer rollout's output wave, two steps ahead of the rules wave)
-__device__ __forceinline__ uint32_t uniform_draw(uint64_t seed, uint64_t table, uint64_t ply) {
-    return philox4x32(make_uint4((uint32_t)table, (uint32_t)(table >> 32), (uint32_t)ply, (uint32_t)(ply >> 32)),
-                      make_uint2((uint32_t)seed, (uint32_t)(seed >> 32))).x;
-}
-// uniform-random legal action from a drawn word: scaled to the legal count, the k-th legal action
-__device__ __forceinline__ int sample_uniform_word(uint64_t m, uint32_t rx) {
-    const int n = __popcll(m);
-    if (n == 0) return 0;
-    int k = (int)(((uint64_t)rx * (uint64_t)n) >> 32);
-    // position of the k-th set bit
-    uint64_t mm = m;
-    int pos = 0;
-#pragma unroll
-    for (int width = 32; width >= 1; width >>= 1) {
-        const uint64_t low = mm & ((1ull << width) - 1ull);
-        const int c = __popcll(low);
-        const bool up = k >= c;
-        k -= up ? c : 0;
-        pos += up ? width : 0;
-        mm = up ? (mm >> width) : low;
-    }
-    return pos;
-}
-// uniform-random legal action: Philox(seed; table, ply) scaled to the legal count
-__device__ __forceinline__ int sample_uniform(uint64_t m, uint64_t seed, uint64_t table, uint64_t ply) {
-    return sample_uniform_word(m, uniform_draw(seed, table, ply));
-}
-
-// scripts/eval_suite.py opponents over a 45-bit legal mask; their random choices are Philox
-// draws (sample_uniform over the preferred subset) where the reference calls np.random.choice.
-constexpr uint64_t kBuyBits = (((1ull << 12) - 1ull) << 15) | (7ull << 42);  // 15..26, 42..44
-constexpr uint64_t kTake2Bits = 0x1Full << 10, kTake3Bits = 0x3FFull, kReserveBits = ((1ull << 15) - 1ull) << 27;
-__device__ __forceinline__ int lowest_action(uint64_t m) { return m ? __ffsll((unsigned long long)m) - 1 : 0; }
-
+// the fused policies (spl_scripted.h) for a table whose state is in registers
 template <int P>
 __device__ __forceinline__ int policy_action(int policy, uint64_t m, const Tab<P> &T, const Consts &L,
                                              uint64_t seed, uint64_t table, uint64_t ply) {
-    if (policy == SPL_POLICY_GREEDY_V1) {  // eval_suite.py:9-29: first legal buy, take-2, take-3, reserve
-        const uint64_t pick = (m & kBuyBits) ? (m & kBuyBits)
-                              : (m & kTake2Bits) ? (m & kTake2Bits)
-                              : (m & kTake3Bits) ? (m & kTake3Bits)
-                              : (m & kReserveBits) ? (m & kReserveBits) : m;
-        return lowest_action(pick);
-    }
-    if (policy == SPL_POLICY_BASIC_PRIORITY) {  // eval_suite.py:32-78
-        const uint64_t vis = m & (((1ull << 12) - 1ull) << 15);
-        uint64_t pick;
-        if (vis) {  // visible buys with the most points (board points: obs[32 + 13k + 2])
-            int best = -1;
-            uint64_t best_set = 0;
-#pragma unroll
-            for (int k = 0; k < 12; ++k) {
-                const bool legal = (vis >> (15 + k)) & 1ull;
-                const int pts = (int)bget(card_rec(L, board_get(T.sw, k)).x, 2);
-                const bool better = legal && pts > best, tie = legal && pts == best;
-                best_set = better ? (1ull << (15 + k)) : (tie ? (best_set | (1ull << (15 + k))) : best_set);
-                best = better ? pts : best;
-            }
-            pick = best_set;
-        } else {
-            pick = (m & (7ull << 42)) ? (m & (7ull << 42))
-                   : (m & kTake3Bits) ? (m & kTake3Bits)
-                   : (m & kTake2Bits) ? (m & kTake2Bits)
-                   : (m & kReserveBits) ? (m & kReserveBits) : 0ull;
-            if (!pick) return lowest_action(m);
-        }
-        return sample_uniform(pick, seed, table, ply);
-    }
+    if (policy == SPL_POLICY_GREEDY_V1) return greedy_v1(m);
+    if (policy == SPL_POLICY_BASIC_PRIORITY)  // board points: obs[32 + 13k + 2]
+        return basic_priority(m, [&](int k, bool) { return (int)bget(card_rec(L, board_get(T.sw, k)).x, 2); }, seed,
+                              table, ply);
     return sample_uniform(m, seed, table, ply);
 }
 
@@ -3930,7 +3852,7 @@ struct spl_ctx_s {
 
 static thread_local std::string g_err;
 
-// shared with spl_policy.hip
+// every translation unit's error channel (spl_common.h)
 int spl_fail(int code, const std::string &msg) {
     g_err = msg;
     return code;
@@ -3963,11 +3885,7 @@ static KArena karena(const spl_arena_t *a) {
                   reinterpret_cast<uint32_t *>(b + L.legal)};
 }
 
-static int launch_check() {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SPL_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return SPL_OK;
-}
+static int launch_check() { return spl_launched("kernel launch"); }
 
 static inline unsigned blocks_for(int64_t n) { return (unsigned)((n + 63) / 64); }
 

@@ -2,62 +2,21 @@
 // scripts/eval_suite.py as a kernel over a mask and an observation, the legality check before a dual
 // step, the per-table tally after it and the reduction per opponent group.
 //
-// The step kernel fuses three of the policies (spl_engine.hip policy_action, inlined into the rollout
-// kernels, whose register allocation a new branch there could move).  This file restates what they need
-// — the uniform draw, the k-th set bit, the action-class bits — word for word, and
-// tests/test_gpu_eval_league.py pins the restatement to the original action by action.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <string>
-
-#include "../../include/splendor_amd.h"
+// The step kernel fuses three of the policies (spl_engine.hip policy_action, fed from the table's state);
+// k_scripted runs the same functions of spl_scripted.h fed from the observation, and adds greedy_v2.
+// tests/test_gpu_eval_league.py pins the observation-fed kernel to the state-fed one action by action.
 #include "../../include/splendor_eval.h"
-#include "spl_rng.h"
-
-int spl_fail(int code, const std::string &msg);  // spl_engine.hip
+#include "spl_common.h"
+#include "spl_scripted.h"
 
 namespace sple {
 
-using spl::philox4x32;
+using namespace spl;  // kActions, kObsDim; the mask classes, samplers and cascades of spl_scripted.h
 
-constexpr int kActions = 45, kObsDim = 297;
 constexpr int kBank = 0;           // obs[0:5]: the bank's coloured tokens (engine/encode.py)
 constexpr int kBoard = 32;         // obs[32 + 13k ..]: visible card k; its points at + 2
 constexpr int kOppPrestige = 30;   // obs: the other player's prestige
 constexpr int kTurnCount = 293;    // obs: turn_count
-
-// ---- restated from spl_engine.hip ------------------------------------------------------------
-__device__ __forceinline__ uint32_t uniform_draw(uint64_t seed, uint64_t table, uint64_t ply) {
-    return philox4x32(make_uint4((uint32_t)table, (uint32_t)(table >> 32), (uint32_t)ply, (uint32_t)(ply >> 32)),
-                      make_uint2((uint32_t)seed, (uint32_t)(seed >> 32))).x;
-}
-// uniform-random legal action from a drawn word: scaled to the legal count, the k-th legal action
-__device__ __forceinline__ int sample_uniform_word(uint64_t m, uint32_t rx) {
-    const int n = __popcll(m);
-    if (n == 0) return 0;
-    int k = (int)(((uint64_t)rx * (uint64_t)n) >> 32);
-    uint64_t mm = m;
-    int pos = 0;
-#pragma unroll
-    for (int width = 32; width >= 1; width >>= 1) {
-        const uint64_t low = mm & ((1ull << width) - 1ull);
-        const int c = __popcll(low);
-        const bool up = k >= c;
-        k -= up ? c : 0;
-        pos += up ? width : 0;
-        mm = up ? (mm >> width) : low;
-    }
-    return pos;
-}
-constexpr uint64_t kVisBuyBits = ((1ull << 12) - 1ull) << 15, kResBuyBits = 7ull << 42;  // 15..26; 42..44
-constexpr uint64_t kBuyBits = kVisBuyBits | kResBuyBits;
-constexpr uint64_t kTake2Bits = 0x1Full << 10, kTake3Bits = 0x3FFull, kReserveBits = ((1ull << 15) - 1ull) << 27;
-__device__ __forceinline__ int lowest_action(uint64_t m) { return m ? __ffsll((unsigned long long)m) - 1 : 0; }
-// take-3 colour sets in itertools.combinations(range(5), 3) order (engine/encode.py:33)
-constexpr uint64_t kTake3Masks = (0x07ull) | (0x0Bull << 5) | (0x13ull << 10) | (0x0Dull << 15) | (0x15ull << 20) |
-                                 (0x19ull << 25) | (0x0Eull << 30) | (0x16ull << 35) | (0x1Aull << 40) | (0x1Cull << 45);
-// -----------------------------------------------------------------------------------------------
 
 // one observation value of row t, from whichever form the caller gave (the values read here are < 256)
 struct ObsRow {
@@ -65,39 +24,6 @@ struct ObsRow {
     const uint8_t *o8;
     __device__ __forceinline__ int operator[](int i) const { return o32 ? o32[i] : (int)o8[i]; }
 };
-
-__device__ __forceinline__ int greedy_v1(uint64_t m) {
-    const uint64_t pick = (m & kBuyBits) ? (m & kBuyBits)
-                          : (m & kTake2Bits) ? (m & kTake2Bits)
-                          : (m & kTake3Bits) ? (m & kTake3Bits)
-                          : (m & kReserveBits) ? (m & kReserveBits) : m;
-    return lowest_action(pick);
-}
-
-__device__ __forceinline__ int basic_priority(uint64_t m, const ObsRow &o, uint64_t seed, uint64_t key, uint64_t ply) {
-    const uint64_t vis = m & kVisBuyBits;
-    uint64_t pick;
-    if (vis) {  // visible buys with the most points
-        int best = -1;
-        uint64_t best_set = 0;
-#pragma unroll
-        for (int k = 0; k < 12; ++k) {
-            const bool legal = (vis >> (15 + k)) & 1ull;
-            const int pts = legal ? o[kBoard + 13 * k + 2] : 0;
-            const bool better = legal && pts > best, tie = legal && pts == best;
-            best_set = better ? (1ull << (15 + k)) : (tie ? (best_set | (1ull << (15 + k))) : best_set);
-            best = better ? pts : best;
-        }
-        pick = best_set;
-    } else {
-        pick = (m & kResBuyBits) ? (m & kResBuyBits)
-               : (m & kTake3Bits) ? (m & kTake3Bits)
-               : (m & kTake2Bits) ? (m & kTake2Bits)
-               : (m & kReserveBits) ? (m & kReserveBits) : 0ull;
-        if (!pick) return lowest_action(m);
-    }
-    return sample_uniform_word(pick, uniform_draw(seed, key, ply));
-}
 
 // eval_suite.py:89-128 with env_ref.state.bank = obs[0:5]
 __device__ __forceinline__ int greedy_v2(uint64_t m, const ObsRow &o) {
@@ -122,7 +48,7 @@ __device__ __forceinline__ int greedy_v2(uint64_t m, const ObsRow &o) {
     }
 #pragma unroll
     for (int a = 0; a < 10; ++a) {
-        const uint32_t cs = (uint32_t)(kTake3Masks >> (5 * a)) & 31u;
+        const uint32_t cs = take3_mask(a);
         int sum = 0;
 #pragma unroll
         for (int c = 0; c < 5; ++c) sum += ((cs >> c) & 1u) ? bank[c] : 0;
@@ -170,9 +96,11 @@ __global__ __launch_bounds__(64) void k_scripted(int n, spl_eval_act_t a) {
     const uint64_t ply = a.ply + (a.ply_base ? (uint64_t)*a.ply_base : 0ull);
     int act;
     if (policy == SPL_POLICY_GREEDY_V1) act = greedy_v1(m);
-    else if (policy == SPL_POLICY_BASIC_PRIORITY) act = basic_priority(m, o, a.seed, key, ply);
+    else if (policy == SPL_POLICY_BASIC_PRIORITY)  // o by value: by reference the registers are allocated otherwise
+        act = basic_priority(m, [o](int k, bool legal) { return legal ? o[kBoard + 13 * k + 2] : 0; }, a.seed, key,
+                             ply);
     else if (policy == SPL_POLICY_GREEDY_V2) act = greedy_v2(m, o);
-    else act = sample_uniform_word(m, uniform_draw(a.seed, key, ply));
+    else act = sample_uniform(m, a.seed, key, ply);
     a.action[t] = act;
 }
 
@@ -227,13 +155,6 @@ __global__ __launch_bounds__(256) void k_reduce(int n, spl_eval_reduce_t r) {
     if (threadIdx.x < SPL_EVAL_COLS) r.out[(size_t)g * SPL_EVAL_COLS + threadIdx.x] = part[threadIdx.x][0];
 }
 
-static int launched(const char *what) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SPL_OK : spl_fail(SPL_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
-static bool misaligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-
 }  // namespace sple
 
 using namespace sple;
@@ -247,24 +168,24 @@ int spl_eval_scripted_act(int32_t n, const spl_eval_act_t *a, void *stream) {
     if (!a) return spl_fail(SPL_E_ARG, "null scripted-act arguments");
     if (!a->mask || !a->action) return spl_fail(SPL_E_ARG, "null buffer: mask and action are required");
     if (!a->obs == !a->obs_u8) return spl_fail(SPL_E_ARG, "exactly one of obs and obs_u8 must be given");
-    if (misaligned(a->obs, 4) || misaligned(a->obs_u8, 4) || misaligned(a->action, 4) || misaligned(a->policy_of, 4))
+    if (spl_misaligned(a->obs, 4) || spl_misaligned(a->obs_u8, 4) || spl_misaligned(a->action, 4) || spl_misaligned(a->policy_of, 4))
         return spl_fail(SPL_E_ARG, "obs, obs_u8, action and policy_of must be 4-byte aligned");
-    if (misaligned(a->table_key, 8) || misaligned(a->ply_base, 8) || misaligned(a->errors, 8))
+    if (spl_misaligned(a->table_key, 8) || spl_misaligned(a->ply_base, 8) || spl_misaligned(a->errors, 8))
         return spl_fail(SPL_E_ARG, "table_key, ply_base and errors must be 8-byte aligned");
     if (!a->policy_of && a->policy != SPL_EVAL_KEEP && (a->policy < SPL_POLICY_UNIFORM || a->policy > SPL_POLICY_GREEDY_V2))
         return spl_fail(SPL_E_ARG, "unknown policy");
     hipLaunchKernelGGL(k_scripted, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, n, *a);
-    return launched("k_scripted");
+    return spl_launched("k_scripted");
 }
 
 int spl_eval_check(int32_t n, const spl_eval_check_t *a, void *stream) {
     if (n < 1) return spl_fail(SPL_E_ARG, "n must be positive");
     if (!a) return spl_fail(SPL_E_ARG, "null check arguments");
     if (!a->action || !a->mask || !a->playing || !a->checks || !a->illegal) return spl_fail(SPL_E_ARG, "null buffer");
-    if (misaligned(a->action, 4) || misaligned(a->checks, 4) || misaligned(a->illegal, 4))
+    if (spl_misaligned(a->action, 4) || spl_misaligned(a->checks, 4) || spl_misaligned(a->illegal, 4))
         return spl_fail(SPL_E_ARG, "action, checks and illegal must be 4-byte aligned");
     hipLaunchKernelGGL(k_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, *a);
-    return launched("k_check");
+    return spl_launched("k_check");
 }
 
 int spl_eval_tally(int32_t n, const spl_eval_tally_t *a, void *stream) {
@@ -273,11 +194,11 @@ int spl_eval_tally(int32_t n, const spl_eval_tally_t *a, void *stream) {
     if (!a->done || !a->game_ended_on || !a->agent_step_reward || !a->opp_reward || !a->final_obs || !a->playing ||
         !a->result || !a->turns || !a->prestige)
         return spl_fail(SPL_E_ARG, "null buffer");
-    if (misaligned(a->agent_step_reward, 4) || misaligned(a->opp_reward, 4) || misaligned(a->final_obs, 4) ||
-        misaligned(a->turns, 4) || misaligned(a->prestige, 4))
+    if (spl_misaligned(a->agent_step_reward, 4) || spl_misaligned(a->opp_reward, 4) || spl_misaligned(a->final_obs, 4) ||
+        spl_misaligned(a->turns, 4) || spl_misaligned(a->prestige, 4))
         return spl_fail(SPL_E_ARG, "rewards, final_obs, turns and prestige must be 4-byte aligned");
     hipLaunchKernelGGL(k_tally, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, *a);
-    return launched("k_tally");
+    return spl_launched("k_tally");
 }
 
 int spl_eval_reduce(int32_t n, int32_t G, const spl_eval_reduce_t *a, void *stream) {
@@ -286,12 +207,12 @@ int spl_eval_reduce(int32_t n, int32_t G, const spl_eval_reduce_t *a, void *stre
     if (!a) return spl_fail(SPL_E_ARG, "null reduce arguments");
     if (!a->playing || !a->result || !a->turns || !a->prestige || !a->checks || !a->illegal || !a->out)
         return spl_fail(SPL_E_ARG, "null buffer");
-    if (misaligned(a->out, 8)) return spl_fail(SPL_E_ARG, "out must be 8-byte aligned");
-    if (misaligned(a->group_of, 4) || misaligned(a->turns, 4) || misaligned(a->prestige, 4) || misaligned(a->checks, 4) ||
-        misaligned(a->illegal, 4))
+    if (spl_misaligned(a->out, 8)) return spl_fail(SPL_E_ARG, "out must be 8-byte aligned");
+    if (spl_misaligned(a->group_of, 4) || spl_misaligned(a->turns, 4) || spl_misaligned(a->prestige, 4) || spl_misaligned(a->checks, 4) ||
+        spl_misaligned(a->illegal, 4))
         return spl_fail(SPL_E_ARG, "group_of, turns, prestige, checks and illegal must be 4-byte aligned");
     hipLaunchKernelGGL(k_reduce, dim3((unsigned)G), dim3(256), 0, (hipStream_t)stream, n, *a);
-    return launched("k_reduce");
+    return spl_launched("k_reduce");
 }
 
 }  // extern "C"

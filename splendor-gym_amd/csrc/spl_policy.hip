@@ -32,7 +32,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kObs = 297, kAct = 45, kHid = 256;
+constexpr int kObs = kObsDim, kAct = kActions, kHid = 256;
 constexpr int kK1 = 19;  // layer-1 k-steps of 16: 297 inputs padded to 304
 constexpr int kK2 = 16;  // layers 2 and 3: 256 inputs
 constexpr int kChunk = 20480, kBiasOff = 19 * 1024;
@@ -467,9 +467,7 @@ int spl_policy_pack(const spl_mlp_t *actor, const spl_mlp_t *critic, int32_t pre
     const int chunks = critic ? kAllChunks : kActorChunks;
     hipLaunchKernelGGL(k_pack, dim3(chunks), dim3(256), 0, (hipStream_t)stream, A, C, critic ? 1 : 0,
                        static_cast<uint8_t *>(packed));
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return spl_fail(SPL_E_HIP, std::string("k_pack launch: ") + hipGetErrorString(e));
-    return SPL_OK;
+    return spl_launched("k_pack launch");
 }
 
 // the observation: int32 obs (16-byte aligned), or (fp32 images) the compact obs_u8 rows
@@ -524,9 +522,7 @@ int spl_policy_act(const void *packed, int64_t packed_bytes, int32_t n, const sp
         hipLaunchKernelGGL((k_act<false, true>), grid, block, 0, s, W, a);
     else
         hipLaunchKernelGGL((k_act<false, false>), grid, block, 0, s, W, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return spl_fail(SPL_E_HIP, std::string("k_act launch: ") + hipGetErrorString(e));
-    return SPL_OK;
+    return spl_launched("k_act launch");
 }
 
 int64_t spl_policy_group_scratch_bytes(int32_t n, int32_t n_images) {

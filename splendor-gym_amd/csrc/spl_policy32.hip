@@ -77,7 +77,7 @@ struct FmtF16x2 {   // SPL_PREC_FP32_F16X2: 22 significant bits in two fp16 plan
 };
 
 constexpr float kTwoLog2e = 2.8853900817779268f;  // 2 log2(e): exp(2|x|) = exp2(2 log2(e) |x|)
-constexpr int kObs = 297, kAct = 45, kHid = 256;
+constexpr int kObs = kObsDim, kAct = kActions, kHid = 256;
 constexpr int kKs1 = 10;    // layer-1 k-steps of 32: 297 inputs padded to 320
 constexpr int kKs2 = 8;     // layers 2 and 3: 256 inputs
 constexpr int kFrag = 1024;                       // one plane of one k-step: [lane][8 elements]
@@ -1107,9 +1107,7 @@ int splp32_pack(const spl_mlp_t *actor, const spl_mlp_t *critic, void *packed, v
     else
         hipLaunchKernelGGL(k_pack32, dim3(critic ? kAllChunks : kActorChunks), dim3(256), 0, (hipStream_t)stream, A, C,
                            critic ? 1 : 0, static_cast<uint8_t *>(packed));
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return spl_fail(SPL_E_HIP, std::string("k_pack32 launch: ") + hipGetErrorString(e));
-    return SPL_OK;
+    return spl_launched("k_pack32 launch");
 }
 
 // ---- grouping: counting sort of tables by network ------------------------------------------
@@ -1257,7 +1255,5 @@ int splp32_act(const uint8_t *img, bool has_critic, bool critic, bool sample, in
         else if (sample) hipLaunchKernelGGL(k_act32_narrow<true>, ngrid, nblock, 0, s, W, a);
         else hipLaunchKernelGGL(k_act32_narrow<false>, ngrid, nblock, 0, s, W, a);
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return spl_fail(SPL_E_HIP, std::string("k_act32 launch: ") + hipGetErrorString(e));
-    return SPL_OK;
+    return spl_launched("k_act32 launch");
 }

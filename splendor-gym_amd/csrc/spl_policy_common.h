@@ -2,16 +2,9 @@
 // the fp32 formats) share: the network a pack kernel reads, the wave-level LDS hand-off, the action
 // draw of the sampling epilogues, and the entry points spl_policy.hip forwards the fp32 images to.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <string>
-
-#include "../../include/splendor_amd.h"
 #include "../../include/splendor_policy.h"
+#include "spl_common.h"
 #include "spl_rng.h"
-
-int spl_fail(int code, const std::string &msg);  // spl_engine.hip: sets spl_last_error()
 
 namespace splpol {
 
@@ -22,12 +15,9 @@ struct PackNet {
 };
 inline PackNet pack_net(const spl_mlp_t *m, int out) { return PackNet{m->w1, m->b1, m->w2, m->b2, m->w3, m->b3, out}; }
 
-// this wave's LDS writes are visible to its own lanes' reads behind this
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
-    __builtin_amdgcn_wave_barrier();
-}
+using spl::kActions;
+using spl::kObsDim;
+using spl::wave_lds_sync;
 
 typedef __attribute__((address_space(3))) void lds_void;
 

@@ -8,15 +8,8 @@
 // builds it).
 #pragma clang fp contract(off)
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <string>
-
-#include "../../include/splendor_amd.h"
 #include "../../include/splendor_ppo.h"
-
-int spl_fail(int code, const std::string &msg);  // spl_engine.hip
+#include "spl_common.h"
 
 namespace splp {
 
@@ -269,13 +262,6 @@ __global__ __launch_bounds__(kBlock) void k_gather(int B, int64_t total, spl_ppo
     }
 }
 
-static int launched(const char *what) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SPL_OK : spl_fail(SPL_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
-static bool misaligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-
 }  // namespace splp
 
 using namespace splp;
@@ -289,17 +275,17 @@ int spl_ppo_record(int32_t n, const spl_ppo_record_t *a, void *stream) {
         !a->done != !a->dst_done)
         return spl_fail(SPL_E_ARG, "null buffer: a record group needs its source and its destination");
     if (!a->obs_u8 && !a->mask && !a->reward && !a->done) return spl_fail(SPL_E_ARG, "null buffer: nothing to record");
-    if (misaligned(a->obs_u8, 4) || misaligned(a->dst_obs_u8, 4))
+    if (spl_misaligned(a->obs_u8, 4) || spl_misaligned(a->dst_obs_u8, 4))
         return spl_fail(SPL_E_ARG, "obs_u8 rows must be 4-byte aligned");
-    if (misaligned(a->dst_mask_bits, 8)) return spl_fail(SPL_E_ARG, "mask_bits must be 8-byte aligned");
-    if (misaligned(a->reward, 4) || misaligned(a->dst_reward, 4))
+    if (spl_misaligned(a->dst_mask_bits, 8)) return spl_fail(SPL_E_ARG, "mask_bits must be 8-byte aligned");
+    if (spl_misaligned(a->reward, 4) || spl_misaligned(a->dst_reward, 4))
         return spl_fail(SPL_E_ARG, "reward rows must be 4-byte aligned");
     Rec r{};
     const int64_t dwords = (int64_t)n * (SPL_PPO_OBS_U8 / 4);
     if (a->obs_u8) {
         r.obs = reinterpret_cast<const uint32_t *>(a->obs_u8);
         r.dst_obs = reinterpret_cast<uint32_t *>(a->dst_obs_u8);
-        const bool wide = !misaligned(a->obs_u8, 16) && !misaligned(a->dst_obs_u8, 16);
+        const bool wide = !spl_misaligned(a->obs_u8, 16) && !spl_misaligned(a->dst_obs_u8, 16);
         r.quads = wide ? dwords / 4 : 0;
         r.tail = dwords - 4 * r.quads;
     }
@@ -312,7 +298,7 @@ int spl_ppo_record(int32_t n, const spl_ppo_record_t *a, void *stream) {
     const int64_t items = r.quads + r.tail, threads = items > n ? items : (int64_t)n;
     hipLaunchKernelGGL(k_record, dim3((unsigned)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream,
                        n, r);
-    return launched("k_record");
+    return spl_launched("k_record");
 }
 
 int64_t spl_ppo_gae_scratch_bytes(int32_t T) {
@@ -327,8 +313,8 @@ int spl_ppo_gae(int32_t K, int32_t T, const spl_ppo_gae_t *a, void *stream) {
         return spl_fail(SPL_E_ARG, "null buffer");
     if (!(a->gamma >= 0.0 && a->gamma <= 1.0) || !(a->lambda >= 0.0 && a->lambda <= 1.0))
         return spl_fail(SPL_E_ARG, "gamma and lambda must be in [0, 1]");
-    if (misaligned(a->reward, 4) || misaligned(a->value, 4) || misaligned(a->last_value, 4) || misaligned(a->adv, 4) ||
-        misaligned(a->ret, 4) || misaligned(a->stats, 8) || misaligned(a->scratch, 8))
+    if (spl_misaligned(a->reward, 4) || spl_misaligned(a->value, 4) || spl_misaligned(a->last_value, 4) || spl_misaligned(a->adv, 4) ||
+        spl_misaligned(a->ret, 4) || spl_misaligned(a->stats, 8) || spl_misaligned(a->scratch, 8))
         return spl_fail(SPL_E_ARG, "float planes must be 4-byte aligned, stats and scratch 8-byte aligned");
     const Gae g{a->reward, a->value, a->done, a->last_value, a->adv, a->ret, a->gamma * a->lambda, (float)a->gamma};
     const int blocks = (T + kBlock - 1) / kBlock;
@@ -336,7 +322,7 @@ int spl_ppo_gae(int32_t K, int32_t T, const spl_ppo_gae_t *a, void *stream) {
     double *partial = static_cast<double *>(a->scratch);
     hipLaunchKernelGGL(k_gae, dim3(blocks), dim3(kBlock), 0, s, K, T, g, partial);
     hipLaunchKernelGGL(k_gae_finish, dim3(1), dim3(kBlock), 0, s, blocks, (uint64_t)K * (uint64_t)T, partial, a->stats);
-    return launched("k_gae");
+    return spl_launched("k_gae");
 }
 
 int spl_ppo_gather(int32_t B, const spl_ppo_gather_t *a, void *stream) {
@@ -347,16 +333,16 @@ int spl_ppo_gather(int32_t B, const spl_ppo_gather_t *a, void *stream) {
         !a->out_obs || !a->out_mask || !a->out_action || !a->out_logprob || !a->out_value || !a->out_adv ||
         !a->out_ret || !a->errors || (a->normalize && !a->stats))
         return spl_fail(SPL_E_ARG, "null buffer");
-    if (misaligned(a->obs_u8, 4)) return spl_fail(SPL_E_ARG, "obs_u8 rows must be 4-byte aligned");
-    if (misaligned(a->idx, 8) || misaligned(a->mask_bits, 8) || misaligned(a->out_action, 8) ||
-        misaligned(a->errors, 8) || misaligned(a->stats, 8))
+    if (spl_misaligned(a->obs_u8, 4)) return spl_fail(SPL_E_ARG, "obs_u8 rows must be 4-byte aligned");
+    if (spl_misaligned(a->idx, 8) || spl_misaligned(a->mask_bits, 8) || spl_misaligned(a->out_action, 8) ||
+        spl_misaligned(a->errors, 8) || spl_misaligned(a->stats, 8))
         return spl_fail(SPL_E_ARG, "idx, mask_bits, out_action, errors and stats must be 8-byte aligned");
-    if (misaligned(a->out_obs, 4) || misaligned(a->out_mask, 4))
+    if (spl_misaligned(a->out_obs, 4) || spl_misaligned(a->out_mask, 4))
         return spl_fail(SPL_E_ARG, "float outputs must be 4-byte aligned");
     const int rows = kBlock / 64;
     hipLaunchKernelGGL(k_gather, dim3((unsigned)((B + rows - 1) / rows)), dim3(kBlock), 0, (hipStream_t)stream, B,
                        (int64_t)a->K * a->T, *a);
-    return launched("k_gather");
+    return spl_launched("k_gather");
 }
 
 }  // extern "C"

@@ -36,13 +36,15 @@ def compact(obs):
 
 
 # ---------------------------------------------------------------------------------------------
-# (a) the restated policies against the step kernel's
+# (a) the observation-fed policies against the step kernel's state-fed ones
 # ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("policy", [0, 1, 2])
 def test_scripted_kernel_equals_fused_policies(policy):
     """After every step of 40 plies of uniform play the scripted kernel, on the step's own obs / mask
     with the same seed, ply and table keys, answers exactly what policy_action answered inside the step
-    kernel — from int32 rows, from compact rows, and with the ply split into ply = 1 + a device base."""
+    kernel — from int32 rows, from compact rows, and with the ply split into ply = 1 + a device base.
+    Both run the cascades of csrc/spl_scripted.h: this pins the kernel that feeds them from the observation
+    to the one that feeds them from the table's state."""
     import torch
     from splendor_gym.device import Engine
     names = {0: "random", 1: "greedy_v1", 2: "basic_priority"}

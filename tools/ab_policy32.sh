@@ -3,29 +3,19 @@
 #   BUILD=1 tools/ab_policy32.sh            # here: the variants below into splendor-gym_amd/ablate/
 #   tools/ab_policy32.sh [rounds]           # GPU box: tools/bench_policy.py per variant, `rounds` passes
 # Variants: name:REV:FLAGS (REV = a git revision of the sources, or "wt" for the working tree; FLAGS, comma
-# separated, are added to the product's).  Every source is compiled with the flags csrc/Makefile gives it.
+# separated, are added to the product's).  BUILD=1 is csrc/Makefile's variant rule through tools/variants.py:
+# spl_policy32.hip (REV's, with REV's headers) recompiled, the other objects the product's own.
 set -o pipefail
 D=splendor-gym_amd/ablate
-C=splendor-gym_amd/csrc
 VARIANTS=${VARIANTS:-"head:HEAD: wt:wt:"}
-flags_of() { make -s -C $C flags-$1; }
 if [ "${BUILD:-0}" = "1" ]; then
-  mkdir -p $D/obj
-  others=""
-  for s in $(make -s -C $C names); do
-    [ $s = spl_policy32 ] && continue
-    others="$others $D/obj/$s.o"
-    [ $D/obj/$s.o -nt $C/$s.hip ] || /opt/rocm/bin/hipcc $(flags_of $s) -c -o $D/obj/$s.o $C/$s.hip || exit 1
-  done
+  specs=""
   for v in $VARIANTS; do
     IFS=: read -r name rev extra <<< "$v"
-    src=$C/spl_policy32.hip
-    if [ "$rev" != "wt" ]; then
-      t=$(mktemp -d); git archive "$rev" $C include | tar -x -C $t; src=$t/$C/spl_policy32.hip
-    fi
-    /opt/rocm/bin/hipcc $(flags_of spl_policy32) ${extra//,/ } -c -o $D/obj/p32v_$name.o $src || exit 1
-    /opt/rocm/bin/hipcc $(flags_of spl_engine) -shared -o $D/libp32v_$name.so $others $D/obj/p32v_$name.o || exit 1
+    [ "$rev" = "wt" ] && rev="" || rev="@$rev"
+    specs="$specs p32v_$name$rev=$extra"
   done
+  python3 tools/variants.py build $specs only=spl_policy32 "lib=$PWD/$D/lib{name}.so" || exit 1
   exit 0
 fi
 O=gpurun_out/ab_p32

@@ -5,7 +5,8 @@ each eager launch, 2p tables, device random policy, refill every 16).
     python tools/ablate.py [--build-only] [--run] [--rollout] [--tables 16384,65536] [--rounds R] [variant ...]
 --rollout times rollout launches (16 steps each) instead of spl_step.  --rounds R alternates the
 variants R times (one process per variant and round) so box drift hits every arm alike.
-Only spl_engine.hip is recompiled per variant; the other objects come from csrc/obj (run `make` first).
+Each variant is csrc/Makefile's `variant` rule (tools/variants.py): spl_engine.hip recompiled with the
+product's flags plus -DSPL_ABL, the other five objects the product's own from csrc/obj, made on demand.
 Outputs are wrong in ablated builds by design; only timings are meaningful.
 """
 import json
@@ -13,8 +14,9 @@ import os
 import subprocess
 import sys
 
+from variants import build_variants
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(REPO, "splendor-gym_amd", "csrc")
 OUTD = os.path.join(REPO, "splendor-gym_amd", "ablate")
 IO = 1 | 2 | 4 | 8 | 32  # every compute phase compiled out: loads + stores only
 # (bits 16, 64, 512 and 2048 were the removed one-wave step kernel's: unused)
@@ -27,32 +29,11 @@ VARIANTS = {"full": 0, "no_legal_pre": 1, "no_apply": 2, "no_legal_post": 4, "no
             "no_final_legal_post": 8 | 4}
 
 
-def _build_one(name, src):
-    bits = VARIANTS[name]
-    out = os.path.join(OUTD, f"lib_{name}.so")
-    obj = os.path.join(OUTD, "obj", f"spl_engine_{name}.o")
-    flags = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950"]
-    subprocess.run(["/opt/rocm/bin/hipcc", *flags, f"-DSPL_ABL={bits}", "-c", "-o", obj,
-                    os.path.join(src, "spl_engine.hip")], check=True)
-    subprocess.run(["/opt/rocm/bin/hipcc", *flags, "-shared", "-o", out, obj,
-                    *[os.path.join(CSRC, "obj", f + ".o") for f in ("spl_policy", "spl_policy32", "spl_dual")]], check=True)
-    return name
-
-
 def build():
-    """Compile the variants in parallel (one hipcc each, at most 8 at once) from a snapshot of the
-    sources, so csrc/ can be edited while they build."""
-    import shutil
-    from concurrent.futures import ThreadPoolExecutor
-    os.makedirs(os.path.join(OUTD, "obj"), exist_ok=True)
-    src = os.path.join(OUTD, "obj", "src")
-    shutil.rmtree(src, ignore_errors=True)
-    shutil.copytree(CSRC, os.path.join(src, "pkg", "csrc"), ignore=shutil.ignore_patterns("obj"))  # ../../include
-    shutil.copytree(os.path.join(REPO, "include"), os.path.join(src, "include"))
+    """Compile the variants (at most ABL_JOBS at once, default 4) into ablate/lib_<name>.so."""
     names = [a for a in sys.argv[1:] if not a.startswith("--") and a in VARIANTS] or list(VARIANTS)
-    with ThreadPoolExecutor(max_workers=int(os.environ.get("ABL_JOBS", "8"))) as ex:
-        for name in ex.map(lambda n: _build_one(n, os.path.join(src, "pkg", "csrc")), names):
-            print("built", name, flush=True)
+    build_variants([dict(name=n, defs=[f"-DSPL_ABL={VARIANTS[n]}"], only=["spl_engine"]) for n in names],
+                   workers=int(os.environ.get("ABL_JOBS", "4")))
 
 
 CHILD = r'''

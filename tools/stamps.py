@@ -1,7 +1,8 @@
 """Per-phase timeline of k_step_ws (spl_step's two-wave kernel) from in-kernel s_memrealtime stamps
 (diagnostic build only).
 
-    python tools/stamps.py            # build lib_stamps.so (-DSPL_STAMPS) and run on the GPU
+    python tools/stamps.py            # build lib_stamps.so (every source with the product's flags plus
+                                      # -DSPL_STAMPS and STAMP_DEFS, tools/variants.py) and run on the GPU
     (STAMP_T: tables, default 65536; --build-only here, --run on the box)
 Lane 0 of every wave stamps its phase boundaries (see STAMP(i) in spl_engine.hip); we report, per
 wave role and phase, the median and max over waves of the time since the kernel's first stamp (10 ns ticks).
@@ -11,6 +12,8 @@ import json
 import os
 import subprocess
 import sys
+
+from variants import build_variant
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.environ.get("STAMP_LIB", os.path.join(REPO, "splendor-gym_amd", "ablate", "lib_stamps.so"))
@@ -48,12 +51,8 @@ print(json.dumps(out))
 
 def main():
     if "--run" not in sys.argv:
-        os.makedirs(os.path.dirname(LIB), exist_ok=True)
         extra = os.environ.get("STAMP_DEFS", "").split()  # e.g. STAMP_DEFS=-DSPL_ABL=4096
-        subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-DSPL_STAMPS",
-                        *extra, "-shared", "-o", LIB, *[os.path.join(REPO, "splendor-gym_amd", "csrc", f)
-                        for f in ("spl_engine.hip", "spl_policy.hip", "spl_policy32.hip", "spl_dual.hip")]],
-                       check=True)
+        build_variant("stamps", ["-DSPL_STAMPS", *extra], lib=LIB)
         if "--build-only" in sys.argv:
             return 0
     env = dict(os.environ, SPLENDOR_AMD_LIB=LIB)

@@ -1,5 +1,6 @@
 """Per-step timeline of the two-wave rollout kernel k_rollout_ws from register-held
-s_memrealtime stamps (diagnostic build -DSPL_STAMPS; not the product library).
+s_memrealtime stamps (diagnostic build, not the product library: every source with the product's flags
+plus -DSPL_STAMPS and STAMP_DEFS, tools/variants.py).
 
     python tools/wsstamps.py [--build-only | --run] [--inplace] [--lib PATH]
     (WS_P / WS_T: players and tables, default 2 and 65536; 4 x 32768 runs the dealer variant)
@@ -11,6 +12,8 @@ import json
 import os
 import subprocess
 import sys
+
+from variants import build_variant
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(REPO, "splendor-gym_amd", "ablate", "lib_wsstamps.so")
@@ -72,12 +75,8 @@ def main():
     if "--lib" in sys.argv:
         lib = sys.argv[sys.argv.index("--lib") + 1]
     if "--run" not in sys.argv:
-        os.makedirs(os.path.dirname(lib), exist_ok=True)
         extra = os.environ.get("STAMP_DEFS", "").split()  # e.g. STAMP_DEFS=-DSPL_ABL=49152
-        subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-DSPL_STAMPS", "-w",
-                        *extra, "-shared", "-o", lib, *[os.path.join(REPO, "splendor-gym_amd", "csrc", f)
-                                                  for f in ("spl_engine.hip", "spl_policy.hip", "spl_policy32.hip", "spl_dual.hip")]],
-                       check=True)
+        build_variant("wsstamps", ["-DSPL_STAMPS", *extra], lib=lib)
         if "--build-only" in sys.argv:
             return 0
     env = dict(os.environ, SPLENDOR_AMD_LIB=lib)
