@@ -1,5 +1,5 @@
 /*
- * splendor_ppo.h — C-ABI of the PPO rollout store (gfx950): record, GAE and minibatch gather.
+ * splendor_ppo.h — C-ABI of the PPO rollout store (gfx950): record, GAE, minibatch gather and loss head.
  *
  * The reference's learner (ppo_splendor.py:287-325) appends per-step numpy copies to Python lists,
  * runs GAE as a numpy loop on the host and re-uploads everything for the update.  These entry points
@@ -12,6 +12,9 @@
  *                    statistics ppo_splendor.py:325 normalises the advantages with
  *   spl_ppo_gather   one minibatch of flat positions, expanded into what
  *                    ActorCritic.get_action_and_value takes
+ *   spl_ppo_loss     the loss head of the update (ppo_splendor.py:337-352) for one minibatch of flat
+ *                    positions: the loss, its statistics and its gradients with respect to the actor's
+ *                    logits and the critic's value, the recorded quantities read from the planes
  *
  * The store is step-major [K][T] (K steps, T tables), every plane caller-owned device memory:
  *   obs_u8     uint8  [K][T][300]  the compact rows of spl_step_args_t.obs_u8 (bytes 0..296 the values
@@ -111,6 +114,58 @@ typedef struct {
     uint64_t *errors;             /* device counter, incremented per bad position (never reset here) */
 } spl_ppo_gather_t;
 
+/* What spl_ppo_loss reports, on the device (56 bytes).  Every mean divides by B, bad rows included in
+ * the divisor and left out of the sums:
+ *   policy_loss = mean(-min(r A, clamp(r, 1-c, 1+c) A))     value_loss = mean(0.5 max((v-ret)^2, (v_c-ret)^2))
+ *   entropy     = mean(H)                                   approx_kl  = mean(lp_old - lp)
+ *   clipfrac    = mean(|r - 1| > c)                         loss = policy_loss + vf_coef value_loss + ent_coef entropy
+ * loss32 = (float)loss; bad = the bad rows of this call. */
+typedef struct {
+    double loss, policy_loss, value_loss, entropy, approx_kl, clipfrac;
+    float loss32;
+    uint32_t bad;
+} spl_ppo_loss_out_t;
+
+/* spl_ppo_loss: the loss head of ppo_splendor.py:337-352 for one minibatch, forward and backward.  Row b
+ * stands for the store's flat position idx[b] = k * T + t (duplicates allowed) and for row b of `logits`
+ * and `new_value`, which the caller's actor and critic computed from that position's observation.
+ * float32 per row, float64 sums over rows.  With L the set bits of the row's mask word (all 45 actions
+ * when no bit is set, ppo_splendor.py:37), a the recorded action, A the advantage (normalised as
+ * spl_ppo_gather does when `normalize`), c = clip_coef:
+ *   p = softmax(logits over L)    lp = log p[a]    H = -SUM_L p log p    r = exp(lp - logprob)
+ *   v_c = value + clamp(v - value, -vclip, vclip)
+ * and the gradients of `loss` are those torch's autograd gives for that expression (min / max split a
+ * tie evenly, clamp passes the gradient on its closed interval):
+ *   g_lp       = -A r / B   when r in [1-c, 1+c] or r A < clamp(r) A, else 0
+ *   dlogits[j] = g_lp (1[j = a] - p_j) - (ent_coef / B) p_j (log p_j + H)   for j in L, exactly 0 otherwise
+ *   dvalue     = (vf_coef / B) (w1 (v - ret) + w2 (v_c - ret) 1[|v - value| <= vclip])
+ *                (w1, w2) = (1, 0) / (0, 1) / (1/2, 1/2) as (v-ret)^2 is above / below / equal to (v_c-ret)^2
+ * A bad row (a position outside [0, K*T), whose address is never formed, or a recorded action outside
+ * L) gets zero gradients, adds nothing to the sums and counts once in *errors and in out->bad.
+ * No floating-point atomics: workgroup partial sums go to `scratch` and are combined in a fixed order,
+ * so two calls on the same inputs give the same bits. */
+typedef struct {
+    int32_t K, T;
+    int32_t normalize;            /* as spl_ppo_gather_t.normalize (0: stats may be NULL)             */
+    int32_t reserved;             /* 0                                                               */
+    const int64_t *idx;           /* [B], 8-byte aligned                                             */
+    const uint64_t *mask_bits;    /* the store's planes: [K][T], 8-byte aligned                      */
+    const int32_t *action;        /* [K][T]                                                          */
+    const float *logprob, *value, *adv, *ret; /* [K][T]                                              */
+    const spl_ppo_stats_t *stats;
+    const float *logits;          /* [B][45] raw actor logits                                        */
+    const float *new_value;       /* [B] the critic's value                                          */
+    float clip_coef, vclip, vf_coef; /* each >= 0                                                    */
+    float ent_coef;               /* signed: positive adds the entropy to the loss (the reference),
+                                     negative subtracts it (the usual bonus)                         */
+    float *dlogits;               /* [B][45] out: d loss / d logits                                  */
+    float *dvalue;                /* [B] out: d loss / d new_value                                   */
+    spl_ppo_loss_out_t *out;      /* out, device, 8-byte aligned                                     */
+    uint64_t *errors;             /* device counter, incremented per bad row (never reset here)      */
+    void *scratch;                /* spl_ppo_loss_scratch_bytes(B) bytes, device, 8-byte aligned; no
+                                     need to clear it                                                */
+} spl_ppo_loss_t;
+
 /* n rows of one step into the store */
 int spl_ppo_record(int32_t n, const spl_ppo_record_t *args, void *stream);
 /* bytes of spl_ppo_gae_t.scratch for T tables (SPL_E_ARG for T < 1) */
@@ -120,6 +175,11 @@ int64_t spl_ppo_gae_scratch_bytes(int32_t T);
 int spl_ppo_gae(int32_t K, int32_t T, const spl_ppo_gae_t *args, void *stream);
 /* one minibatch of B positions, expanded */
 int spl_ppo_gather(int32_t B, const spl_ppo_gather_t *args, void *stream);
+/* bytes of spl_ppo_loss_t.scratch for B rows (SPL_E_ARG for B < 1) */
+int64_t spl_ppo_loss_scratch_bytes(int32_t B);
+/* loss, statistics and gradients of one minibatch of B rows: two launches (the rows with each
+ * workgroup's partial sums, then a one-workgroup finish), asynchronous on `stream`, nothing allocated */
+int spl_ppo_loss(int32_t B, const spl_ppo_loss_t *args, void *stream);
 
 #ifdef __cplusplus
 }

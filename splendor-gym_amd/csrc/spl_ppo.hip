@@ -1,6 +1,7 @@
 // spl_ppo.hip — the PPO rollout store (include/splendor_ppo.h): record one step's rows, the GAE
 // reverse scan of ppo_splendor.py:304-314 with the advantage statistics of :325, and the minibatch
-// gather that expands the compact rows into ActorCritic.get_action_and_value's inputs.
+// gather that expands the compact rows into ActorCritic.get_action_and_value's inputs, and the loss head
+// of the update (loss, statistics and the gradients with respect to the logits and the value).
 //
 // The GAE scan must be bit-equal to numpy, which never fuses a multiply with an add, while HIP device
 // code contracts a*b+c into an FMA by default.  Contraction is switched off for this whole file by
@@ -10,6 +11,8 @@
 
 #include "../../include/splendor_ppo.h"
 #include "spl_common.h"
+
+#include <float.h>
 
 namespace splp {
 
@@ -262,6 +265,192 @@ __global__ __launch_bounds__(kBlock) void k_gather(int B, int64_t total, spl_ppo
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// loss
+// ---------------------------------------------------------------------------------------------
+// A wave owns 64 rows = 2 880 contiguous logits: in as 45 coalesced 64-lane loads into its LDS tile,
+// then lane l works on row l out of the tile (a stride of 45 dwords is odd, so the 64 lanes fall on
+// different banks), puts the row's gradient back in place, and the tile goes out as 45 coalesced
+// stores.  The row's recorded scalars are gathered by idx, one lane per row.  The waves of a workgroup
+// share nothing but the partial sums at the end.
+constexpr int kLossSums = 6;  // policy, value, entropy, lp_old - lp, clipped rows, bad rows
+constexpr uint64_t kAllActions = (1ull << spl::kActions) - 1;
+
+// sum of x over the wave in a fixed order (a butterfly over the lane index); every lane gets it
+__device__ __forceinline__ double wave_sum(double x) {
+#pragma unroll
+    for (int h = 32; h > 0; h >>= 1) x += __shfl_xor(x, h, 64);
+    return x;
+}
+
+// the workgroup's sums of q[0], ... in a fixed order (the butterfly inside each wave, then the waves in
+// order), in every thread
+__device__ __forceinline__ void block_sums(double (&q)[kLossSums], double (*lds)[kLossSums]) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 0; k < kLossSums; ++k) {
+        q[k] = wave_sum(q[k]);
+        if (lane == k) lds[wave][k] = q[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kLossSums; ++k) {
+        q[k] = lds[0][k];
+#pragma unroll
+        for (int w = 1; w < kBlock / 64; ++w) q[k] += lds[w][k];
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_loss(int B, int64_t total, float inv_b, spl_ppo_loss_t g,
+                                                 double *__restrict__ partial) {
+    constexpr int kA = spl::kActions;
+    __shared__ float tile[kBlock / 64][64 * kA];
+    __shared__ double sums[kBlock / 64][kLossSums];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t row0 = ((int64_t)blockIdx.x * (kBlock / 64) + wave) * 64, b = row0 + lane;
+    const int64_t base = row0 * kA, end = (int64_t)B * kA;
+    const bool whole = base + 64 * kA <= end;  // all 64 rows exist: no bound to test per load and store
+    float *t = tile[wave];
+    const int64_t pos = b < B ? g.idx[b] : -1;
+    const bool in = b < B && pos >= 0 && pos < total;  // an address is formed only under `in`
+    uint64_t legal = 0;
+    int act = -1;
+    float lp_old = 0.f, v_old = 0.f, adv = 0.f, ret = 0.f, v = 0.f;
+    if (in) {
+        legal = g.mask_bits[pos] & kAllActions;
+        act = g.action[pos];
+        lp_old = g.logprob[pos];
+        v_old = g.value[pos];
+        adv = g.adv[pos];
+        ret = g.ret[pos];
+        v = g.new_value[b];
+    }
+    // the tile: with all 45 loads in flight at once (and the gathers above beside them) the wave waits
+    // for memory once
+    if (whole) {
+        float in_flight[kA];
+#pragma unroll
+        for (int a = 0; a < kA; ++a) in_flight[a] = g.logits[base + a * 64 + lane];
+#pragma unroll
+        for (int a = 0; a < kA; ++a) t[a * 64 + lane] = in_flight[a];
+    } else {
+#pragma unroll 9
+        for (int a = 0; a < kA; ++a) {
+            const int64_t off = base + a * 64 + lane;
+            if (off < end) t[a * 64 + lane] = g.logits[off];
+        }
+    }
+    if (in && g.normalize) {  // as k_gather
+        const float num = adv - g.stats->mean32, den = g.stats->std32 + 1e-8f;
+        adv = (float)((double)num / (double)den);
+    }
+    if (!legal) legal = kAllActions;
+    const bool ok = in && act >= 0 && act < kA && ((legal >> act) & 1);
+    spl::wave_lds_sync();
+
+    float *row = t + lane * kA;
+    float dv = 0.f;
+    double q[kLossSums] = {0.0, 0.0, 0.0, 0.0, 0.0, (b < B && !ok) ? 1.0 : 0.0};
+    if (ok) {
+        // x[j]: the logit, then logit - max, then log p_j; -inf for an illegal j until log p_j is clamped
+        // to -FLT_MAX, and its p_j = exp(-inf) is an exact 0: every product with it below is a zero, so
+        // the loops need no branch on legality
+        float x[kA];
+        float m = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < kA; ++j) {
+            x[j] = ((legal >> j) & 1) ? row[j] : -INFINITY;
+            m = fmaxf(m, x[j]);
+        }
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < kA; ++j) {
+            x[j] -= m;
+            s += expf(x[j]);
+        }
+        const float logz = logf(s);
+        float H = 0.f, lp = 0.f;
+#pragma unroll
+        for (int j = 0; j < kA; ++j) {
+            const float p = expf(x[j] - logz);
+            const float l = fmaxf(x[j] - logz, -FLT_MAX);  // keeps 0 * log 0 at 0, as torch's entropy() does
+            x[j] = l;
+            row[j] = p;
+            H -= p * l;
+            lp = j == act ? l : lp;
+        }
+        const float c = g.clip_coef, lo = 1.f - c, hi = 1.f + c;
+        const float r = expf(lp - lp_old), rc = fminf(fmaxf(r, lo), hi);
+        const float s1 = r * adv, s2 = rc * adv;
+        const float g_lp = ((r >= lo && r <= hi) || s1 < s2) ? -(adv * r) * inv_b : 0.f;
+        const float g_ent = g.ent_coef * inv_b;
+#pragma unroll
+        for (int j = 0; j < kA; ++j) {
+            const float p = row[j];
+            row[j] = (g_lp * ((j == act ? 1.f : 0.f) - p) - g_ent * p * (x[j] + H)) + 0.f;  // -0 + 0 = +0
+        }
+        const float vclip = g.vclip, dlt = v - v_old;
+        const float v_c = v_old + fminf(fmaxf(dlt, -vclip), vclip);
+        const float e1 = v - ret, e2 = v_c - ret, q1 = e1 * e1, q2 = e2 * e2;
+        const float w1 = q1 > q2 ? 1.f : q1 < q2 ? 0.f : 0.5f;
+        const float through = (dlt >= -vclip && dlt <= vclip) ? (1.f - w1) * e2 : 0.f;
+        dv = g.vf_coef * inv_b * (w1 * e1 + through);
+        q[0] = -(double)fminf(s1, s2);
+        q[1] = (double)(0.5f * fmaxf(q1, q2));
+        q[2] = (double)H;
+        q[3] = (double)(lp_old - lp);
+        q[4] = fabsf(r - 1.f) > c ? 1.0 : 0.0;
+    } else {
+#pragma unroll
+        for (int j = 0; j < kA; ++j) row[j] = 0.f;  // a bad row; past B the tile row is never stored
+    }
+    if (b < B) g.dvalue[b] = dv;
+    spl::wave_lds_sync();
+    if (whole) {
+#pragma unroll
+        for (int a = 0; a < kA; ++a) g.dlogits[base + a * 64 + lane] = t[a * 64 + lane];
+    } else {
+#pragma unroll 9
+        for (int a = 0; a < kA; ++a) {
+            const int64_t off = base + a * 64 + lane;
+            if (off < end) g.dlogits[off] = t[a * 64 + lane];
+        }
+    }
+
+    block_sums(q, sums);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < kLossSums; ++k) partial[(int64_t)blockIdx.x * kLossSums + k] = q[k];
+        if (q[kLossSums - 1] > 0.0)
+            atomicAdd(reinterpret_cast<unsigned long long *>(g.errors), (unsigned long long)q[kLossSums - 1]);
+    }
+}
+
+// one workgroup: lane j adds partials j, j + 256, ... in that order, then block_sums
+__global__ __launch_bounds__(kBlock) void k_loss_finish(int blocks, int B, float vf_coef, float ent_coef,
+                                                        const double *__restrict__ partial,
+                                                        spl_ppo_loss_out_t *__restrict__ o) {
+    __shared__ double sums[kBlock / 64][kLossSums];
+    double q[kLossSums] = {};
+    for (int p = threadIdx.x; p < blocks; p += kBlock) {
+#pragma unroll
+        for (int k = 0; k < kLossSums; ++k) q[k] += partial[(int64_t)p * kLossSums + k];
+    }
+    block_sums(q, sums);
+    if (threadIdx.x == 0) {
+        const double n = (double)B;
+        o->policy_loss = q[0] / n;
+        o->value_loss = q[1] / n;
+        o->entropy = q[2] / n;
+        o->approx_kl = q[3] / n;
+        o->clipfrac = q[4] / n;
+        const double loss = (o->policy_loss + (double)vf_coef * o->value_loss) + (double)ent_coef * o->entropy;
+        o->loss = loss;
+        o->loss32 = (float)loss;
+        o->bad = (uint32_t)q[5];
+    }
+}
+
 }  // namespace splp
 
 using namespace splp;
@@ -343,6 +532,37 @@ int spl_ppo_gather(int32_t B, const spl_ppo_gather_t *a, void *stream) {
     hipLaunchKernelGGL(k_gather, dim3((unsigned)((B + rows - 1) / rows)), dim3(kBlock), 0, (hipStream_t)stream, B,
                        (int64_t)a->K * a->T, *a);
     return spl_launched("k_gather");
+}
+
+int64_t spl_ppo_loss_scratch_bytes(int32_t B) {
+    if (B < 1) return spl_fail(SPL_E_ARG, "B must be positive");
+    return (((int64_t)B + kBlock - 1) / kBlock) * kLossSums * (int64_t)sizeof(double);
+}
+
+int spl_ppo_loss(int32_t B, const spl_ppo_loss_t *a, void *stream) {
+    if (B < 1) return spl_fail(SPL_E_ARG, "B must be positive");
+    if (!a) return spl_fail(SPL_E_ARG, "null loss arguments");
+    if (a->K < 1 || a->T < 1) return spl_fail(SPL_E_ARG, "K and T must be positive");
+    if (!a->idx || !a->mask_bits || !a->action || !a->logprob || !a->value || !a->adv || !a->ret || !a->logits ||
+        !a->new_value || !a->dlogits || !a->dvalue || !a->out || !a->errors || !a->scratch || (a->normalize && !a->stats))
+        return spl_fail(SPL_E_ARG, "null buffer");
+    if (spl_misaligned(a->idx, 8) || spl_misaligned(a->mask_bits, 8) || spl_misaligned(a->stats, 8) ||
+        spl_misaligned(a->out, 8) || spl_misaligned(a->errors, 8) || spl_misaligned(a->scratch, 8))
+        return spl_fail(SPL_E_ARG, "idx, mask_bits, stats, out, errors and scratch must be 8-byte aligned");
+    if (spl_misaligned(a->action, 4) || spl_misaligned(a->logprob, 4) || spl_misaligned(a->value, 4) ||
+        spl_misaligned(a->adv, 4) || spl_misaligned(a->ret, 4) || spl_misaligned(a->logits, 4) ||
+        spl_misaligned(a->new_value, 4) || spl_misaligned(a->dlogits, 4) || spl_misaligned(a->dvalue, 4))
+        return spl_fail(SPL_E_ARG, "action and the float planes must be 4-byte aligned");
+    if (a->clip_coef != a->clip_coef || a->vclip != a->vclip || a->vf_coef != a->vf_coef || a->ent_coef != a->ent_coef)
+        return spl_fail(SPL_E_ARG, "a coefficient is NaN");
+    if (a->clip_coef < 0.f || a->vclip < 0.f || a->vf_coef < 0.f)
+        return spl_fail(SPL_E_ARG, "clip_coef, vclip and vf_coef must not be negative");
+    const int blocks = (int)(((int64_t)B + kBlock - 1) / kBlock);
+    const hipStream_t s = (hipStream_t)stream;
+    double *partial = static_cast<double *>(a->scratch);
+    hipLaunchKernelGGL(k_loss, dim3(blocks), dim3(kBlock), 0, s, B, (int64_t)a->K * a->T, 1.f / (float)B, *a, partial);
+    hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(kBlock), 0, s, blocks, B, a->vf_coef, a->ent_coef, partial, a->out);
+    return spl_launched("k_loss");
 }
 
 }  // extern "C"

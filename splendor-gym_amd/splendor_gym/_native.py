@@ -104,6 +104,21 @@ class PpoGather(ctypes.Structure):
                                         "out_ret", "errors")]
 
 
+class PpoLossOut(ctypes.Structure):
+    """spl_ppo_loss_out_t (include/splendor_ppo.h)"""
+    _fields_ = [(k, ctypes.c_double) for k in ("loss", "policy_loss", "value_loss", "entropy", "approx_kl", "clipfrac")] + \
+               [("loss32", ctypes.c_float), ("bad", ctypes.c_uint32)]
+
+
+class PpoLoss(ctypes.Structure):
+    """spl_ppo_loss_t (include/splendor_ppo.h)"""
+    _fields_ = [("K", c_int32), ("T", c_int32), ("normalize", c_int32), ("reserved", c_int32)] + \
+               [(k, c_void_p) for k in ("idx", "mask_bits", "action", "logprob", "value", "adv", "ret", "stats", "logits",
+                                        "new_value")] + \
+               [(k, ctypes.c_float) for k in ("clip_coef", "vclip", "vf_coef", "ent_coef")] + \
+               [(k, c_void_p) for k in ("dlogits", "dvalue", "out", "errors", "scratch")]
+
+
 EVAL_ABI = 1                       # SPL_EVAL_ABI (include/splendor_eval.h)
 POLICY_GREEDY_V2, EVAL_KEEP = 3, -1  # SPL_POLICY_GREEDY_V2, SPL_EVAL_KEEP: spl_eval_scripted_act only
 EVAL_COLS = 8                      # wins, losses, draws, unfinished, sum turns, sum prestige, checks, illegal
@@ -202,6 +217,8 @@ SIGNATURES = {
     "spl_ppo_gae_scratch_bytes": ([c_int32], c_int64),
     "spl_ppo_gae": ([c_int32, c_int32, ctypes.POINTER(PpoGae), c_void_p], c_int32),
     "spl_ppo_gather": ([c_int32, ctypes.POINTER(PpoGather), c_void_p], c_int32),
+    "spl_ppo_loss_scratch_bytes": ([c_int32], c_int64),
+    "spl_ppo_loss": ([c_int32, ctypes.POINTER(PpoLoss), c_void_p], c_int32),
     # include/splendor_eval.h
     "spl_eval_abi_version": ([], c_int32),
     "spl_eval_scripted_act": ([c_int32, ctypes.POINTER(EvalAct), c_void_p], c_int32),

@@ -12,14 +12,56 @@ masks: 2.8 GB instead of 10.4 GB at 128 steps x 65 536 tables):
     into ``ActorCritic.get_action_and_value``'s float32 inputs) and ``minibatches``;
   * ``collect``  num_steps iterations of the config-5 loop (FusedActorCritic.act on the env's compact
     rows, DualStepVectorEnv.dual_step), recorded, and the bootstrap value; eager or one hipGraph;
-  * ``ppo_update``  the update of ppo_splendor.py:327-361 in torch over ``store.minibatches``.
+  * ``ppo_update``  the update of ppo_splendor.py:327-361 in torch over ``store.minibatches``; with
+    ``fused_loss=True`` its loss head (masked softmax, ratio, clips, means, and their gradients) is
+    ``PPORolloutStore.loss``, one device call on the store's planes.
 
-The learner's forward and backward passes stay in torch.  There is no CPU fallback.
+The two networks' forward and backward passes stay in torch.  There is no CPU fallback.
 """
 import ctypes
 
 from . import _native
-from ._native import NUM_ACTIONS, OBS_DIM, OBS_U8, PpoGae, PpoGather, PpoRecord, check
+from ._native import NUM_ACTIONS, OBS_DIM, OBS_U8, PpoGae, PpoGather, PpoLoss, PpoLossOut, PpoRecord, check
+
+
+class PPOLossOut:
+    """Device views of one spl_ppo_loss_out_t: loss, policy_loss, value_loss, entropy, approx_kl, clipfrac
+    (0-dim float64), loss32 (float32) and bad (the bad rows of the call, int32).  `buf` is the struct as
+    float64 [7]; the views follow whatever the store's next loss() call with the same B writes there."""
+    STATS = ("loss", "policy_loss", "value_loss", "entropy", "approx_kl", "clipfrac")
+
+    def __init__(self, buf, torch):
+        self.buf = buf
+        for i, name in enumerate(self.STATS):
+            setattr(self, name, buf[i])
+        self.loss32 = buf.view(torch.float32)[2 * len(self.STATS)]
+        self.bad = buf.view(torch.int32)[2 * len(self.STATS) + 1]
+
+
+_LOSS_FUNCTION = None
+
+
+def _loss_function(torch):
+    """The autograd node of PPORolloutStore.loss (torch is imported when a store is built, not with
+    this module)."""
+    global _LOSS_FUNCTION
+    if _LOSS_FUNCTION is None:
+        class PpoLossFunction(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, logits, value, store, idx, coef, normalize):
+                ctx.bufs = store._launch_loss(idx, logits, value, coef, normalize)
+                ctx.serial, ctx.value_shape = ctx.bufs["serial"], value.shape
+                return ctx.bufs["out"].loss32.clone()
+
+            @staticmethod
+            def backward(ctx, grad):
+                if ctx.bufs["serial"] != ctx.serial:
+                    raise RuntimeError("PPORolloutStore.loss: a later loss() call with the same B has overwritten "
+                                       "the gradients of this one")
+                return grad * ctx.bufs["dlogits"], (grad * ctx.bufs["dvalue"]).view(ctx.value_shape), None, None, None, None
+
+        _LOSS_FUNCTION = PpoLossFunction
+    return _LOSS_FUNCTION
 
 
 class PPORolloutStore:
@@ -53,6 +95,7 @@ class PPORolloutStore:
         self.mean32 = self._stats.view(torch.float32)[10:11]  # device views for tests and sharded all-reduces
         self.std32 = self._stats.view(torch.float32)[11:12]
         self._scratch = z((int(check(self.lib, self.lib.spl_ppo_gae_scratch_bytes(T))) // 8,), torch.float64)
+        self._loss_bufs = {}  # B -> the buffers of loss(): scratch, dlogits, dvalue, out, the call serial
 
     def _stream(self):
         return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
@@ -145,6 +188,59 @@ class PPORolloutStore:
             check(self.lib, self.lib.spl_ppo_gather(B, ctypes.byref(a), self._stream()))
         return out
 
+    def _loss_buffers(self, B):
+        bufs = self._loss_bufs.get(B)
+        if bufs is None:
+            t = self.torch
+            e = lambda shape, dt: t.empty(shape, dtype=dt, device=self.device)
+            scratch = e((int(check(self.lib, self.lib.spl_ppo_loss_scratch_bytes(B))) // 8,), t.float64)
+            bufs = {"scratch": scratch, "dlogits": e((B, NUM_ACTIONS), t.float32), "dvalue": e((B,), t.float32),
+                    "out": PPOLossOut(t.zeros(ctypes.sizeof(PpoLossOut) // 8, dtype=t.float64, device=self.device), t),
+                    "serial": 0}
+            self._loss_bufs[B] = bufs
+        return bufs
+
+    def _launch_loss(self, idx, logits, value, coef, normalize):
+        bufs = self._loss_buffers(idx.numel())
+        a = PpoLoss(K=self.num_steps, T=self.num_envs, normalize=1 if normalize else 0, reserved=0,
+                    idx=idx.data_ptr(), mask_bits=self.mask_bits.data_ptr(), action=self.action.data_ptr(),
+                    logprob=self.logprob.data_ptr(), value=self.value.data_ptr(), adv=self.adv.data_ptr(),
+                    ret=self.ret.data_ptr(), stats=self._stats.data_ptr(), logits=logits.data_ptr(),
+                    new_value=value.data_ptr(), clip_coef=coef[0], vclip=coef[1], vf_coef=coef[2], ent_coef=coef[3],
+                    dlogits=bufs["dlogits"].data_ptr(), dvalue=bufs["dvalue"].data_ptr(),
+                    out=bufs["out"].buf.data_ptr(), errors=self.errors.data_ptr(), scratch=bufs["scratch"].data_ptr())
+        with self.torch.cuda.device(self.device):
+            check(self.lib, self.lib.spl_ppo_loss(idx.numel(), ctypes.byref(a), self._stream()))
+        bufs["serial"] += 1
+        return bufs
+
+    def loss(self, idx, logits, value, clip_coef=0.2, vclip=0.2, vf_coef=0.5, ent_coef=0.03, entropy_bonus=False,
+             normalize=True):
+        """The loss head of ppo_update as one device call (spl_ppo_loss), forward and backward: idx int64 [B]
+        as for gather, logits float32 [B, 45] (the actor's raw output for those positions' observations),
+        value float32 [B] or [B, 1] (the critic's).  The recorded mask, action, log-probability, value,
+        advantage (normalised when `normalize`) and return are read from the store's planes.
+
+        Returns (loss, out).  loss is a 0-dim float32 tensor whose backward() hands d loss / d logits and
+        d loss / d value to `logits` and `value`.  out (PPOLossOut) holds device views of loss,
+        policy_loss, value_loss, entropy, approx_kl, clipfrac (float64) and bad; reading them does not
+        synchronise until a value is taken to the host.
+
+        The gradients, the statistics and the scratch live in buffers the store owns, one set per B, sized
+        on first use: out, and a pending backward(), belong to the latest loss() call with that B (a
+        backward() after a later call raises).  A position outside the store, or a recorded action outside
+        its mask, is a bad row: zero gradients, left out of the means (which still divide by B), counted
+        in self.errors and out.bad."""
+        t = self.torch
+        if idx.dtype != t.int64 or idx.dim() != 1 or not idx.is_contiguous() or idx.device != self.device or \
+                idx.numel() < 1:
+            raise ValueError(f"idx must be a non-empty contiguous int64 [B] tensor on {self.device}")
+        B = idx.numel()
+        self._own(logits, (t.float32,), (B, NUM_ACTIONS), "logits")
+        self._own(value, (t.float32,), (B, 1) if value.dim() == 2 else (B,), "value")
+        coef = (float(clip_coef), float(vclip), float(vf_coef), -float(ent_coef) if entropy_bonus else float(ent_coef))
+        return _loss_function(t).apply(logits, value, self, idx, coef, bool(normalize)), self._loss_buffers(B)["out"]
+
     def minibatches(self, batch_size, generator=None):
         """One epoch's index tensors: a device randperm of the K * T positions split into pieces of
         batch_size, the last one shorter (ppo_splendor.py:334-336)."""
@@ -215,7 +311,8 @@ def collect(env, agent_k, store, obs, mask, seed=0, table0=0, graph=False):
 
 
 def ppo_update(agent, optimizer, store, clip_coef=0.2, vclip=0.2, ent_coef=0.03, vf_coef=0.5, update_epochs=4,
-               minibatch_size=256, target_kl=0.02, max_grad_norm=0.5, generator=None, entropy_bonus=False):
+               minibatch_size=256, target_kl=0.02, max_grad_norm=0.5, generator=None, entropy_bonus=False,
+               fused_loss=False):
     """The update of ppo_splendor.py:327-361 over store.minibatches (call store.compute_gae first):
     clipped policy loss, clipped value loss, the entropy term, grad-norm clip at 0.5 and the target-KL
     early stop, which like the reference's `break` ends the current epoch only.
@@ -224,9 +321,17 @@ def ppo_update(agent, optimizer, store, clip_coef=0.2, vclip=0.2, ent_coef=0.03,
     (entropy_loss = -entropy; ... + ent_coef * (-entropy_loss)) ADDS the entropy to the minimised loss.
     That is reproduced by default; entropy_bonus=True subtracts it instead (the usual PPO bonus).
 
+    fused_loss=True replaces everything between the two networks and loss.backward() by store.loss (one
+    device call for the loss, its statistics and its gradients); the gather then only supplies the
+    observations.  The arithmetic is the same, in another summation order.
+
     Returns the last minibatch's policy_loss, value_loss, entropy and approx_kl, first_approx_kl (the
-    first minibatch's, evaluated before any optimiser step) and the number of optimiser steps."""
+    first minibatch's, evaluated before any optimiser step) and the number of optimiser steps; with
+    fused_loss also the last minibatch's clipfrac."""
     torch = store.torch
+    if fused_loss:
+        return _ppo_update_fused(agent, optimizer, store, clip_coef, vclip, ent_coef, vf_coef, update_epochs,
+                                 minibatch_size, target_kl, max_grad_norm, generator, entropy_bonus)
     last, first_kl, steps = None, None, 0
     sign = -1.0 if entropy_bonus else 1.0
     for _ in range(int(update_epochs)):
@@ -257,3 +362,29 @@ def ppo_update(agent, optimizer, store, clip_coef=0.2, vclip=0.2, ent_coef=0.03,
     vals = [float(x) for x in last]
     return {"policy_loss": vals[0], "value_loss": vals[1], "entropy": vals[2], "approx_kl": vals[3],
             "first_approx_kl": float(first_kl), "optimizer_steps": steps}
+
+
+def _ppo_update_fused(agent, optimizer, store, clip_coef, vclip, ent_coef, vf_coef, update_epochs, minibatch_size,
+                      target_kl, max_grad_norm, generator, entropy_bonus):
+    """ppo_update(fused_loss=True): the same loop with store.loss as the loss head."""
+    torch = store.torch
+    last, first_kl, steps = None, None, 0
+    for _ in range(int(update_epochs)):
+        for idx in store.minibatches(minibatch_size, generator):
+            obs = store.gather(idx, normalize=True)["obs"]
+            loss, out = store.loss(idx, agent.actor(obs), agent.critic(obs), clip_coef=clip_coef, vclip=vclip,
+                                   vf_coef=vf_coef, ent_coef=ent_coef, entropy_bonus=entropy_bonus, normalize=True)
+            optimizer.zero_grad()
+            loss.backward()
+            torch.nn.utils.clip_grad_norm_(agent.parameters(), max_grad_norm)
+            optimizer.step()
+            steps += 1
+            if first_kl is None:
+                first_kl = out.approx_kl.clone()
+            last = out  # its views hold the latest call with this B, which is this one when the loop ends
+            if target_kl > 0 and out.approx_kl.item() > target_kl:
+                break
+    if last is None:
+        raise ValueError("update_epochs must be at least 1")
+    res = {name: float(getattr(last, name)) for name in ("policy_loss", "value_loss", "entropy", "approx_kl")}
+    return {**res, "first_approx_kl": float(first_kl), "optimizer_steps": steps, "clipfrac": float(last.clipfrac)}

@@ -5,7 +5,8 @@
 The loop of the reference's ppo_splendor.py with its argument names where they apply: rollouts of
 DualStepVectorEnv against an OpponentPool (current policy with --p-current, else one of --pool-size
 snapshots, drawn per episode), the agent's forward fused (FusedActorCritic), the trajectory in a
-PPORolloutStore, GAE on the device, the update in torch (splendor_gym.ppo).  After each update the
+PPORolloutStore, GAE on the device, the update in torch (splendor_gym.ppo; --fused-loss: its loss head
+as one device call).  After each update the
 fused agent and the pool re-pack the new weights; every --snapshot-every-updates updates the pool takes
 a snapshot.  --eval-every-updates N evaluates before training and every N updates, --eval-games games
 against each of random, greedy_v1, basic, the agent itself and greedy_v2 in one batch on the device
@@ -42,6 +43,8 @@ def main(argv=None):
     p.add_argument("--device", type=str, default="cuda:0")
     p.add_argument("--entropy-bonus", action="store_true",
                    help="subtract the entropy term (the usual PPO bonus); default: the reference's sign (ppo_update)")
+    p.add_argument("--fused-loss", action="store_true",
+                   help="the update's loss head as one device call (PPORolloutStore.loss) instead of torch elementwise ops")
     p.add_argument("--no-graph", action="store_true", help="run every rollout eagerly instead of replaying a hipGraph")
     p.add_argument("--eval-every-updates", type=int, default=0,
                    help="evaluate before training and every N updates (0: never), as ppo_splendor.py does")
@@ -101,7 +104,8 @@ def main(argv=None):
         res = ppo_update(agent, optimizer, store, clip_coef=args.clip_coef, vclip=args.vclip,
                          ent_coef=args.ent_coef + (args.ent_coef_final - args.ent_coef) * progress,
                          vf_coef=args.vf_coef, update_epochs=args.update_epochs, minibatch_size=args.minibatch_size,
-                         target_kl=args.target_kl, generator=gen, entropy_bonus=args.entropy_bonus)
+                         target_kl=args.target_kl, generator=gen, entropy_bonus=args.entropy_bonus,
+                         fused_loss=args.fused_loss)
         agent_k.refresh()
         pool.refresh()
         if (update + 1) % max(1, args.snapshot_every_updates) == 0:

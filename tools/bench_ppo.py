@@ -1,8 +1,8 @@
 """Timings of the PPO rollout store (splendor_gym/ppo.py) at the size the engine exists for.
 
-    python tools/bench_ppo.py [--tables 65536] [--steps 128] [--repeats 7]
+    python tools/bench_ppo.py [--tables 65536] [--steps 128] [--repeats 7] [--loss-json FILE]
 
-Prints one JSON line with three comparisons, each arm timed with device events, the arms alternating,
+Prints one JSON line with four comparisons, each arm timed with device events, the arms alternating,
 medians reported:
   1. record: a hipGraph of `steps` config-5 dual steps (tools/bench_selfplay.py's loop: fused fp32 actor,
      opponent pool of 12 trained snapshots) without and with the store's record launches and with the
@@ -11,6 +11,8 @@ medians reported:
      loop's result is compared bit for bit with the kernel's); back to back over the same planes, and once
      per window after 1 GiB of other stores.
   3. gather: spl_ppo_gather at B = 256 and B = 65 536 beside index_select plus the torch expansion.
+  4. loss: PPORolloutStore.loss (spl_ppo_loss) beside the torch loss head of ppo_update, forward and backward
+     from leaf logits / value tensors, at B = 256 and B = 65 536.
 Bytes are the algorithmic bytes each kernel has to move, computed from the shapes below.
 """
 import argparse
@@ -29,6 +31,7 @@ def main():
     ap.add_argument("--steps", type=int, default=128)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--pool-size", type=int, default=12)
+    ap.add_argument("--loss-json", default="", help="also write the loss section to this file (profiles/ppo/bench_ppo_loss.json)")
     args = ap.parse_args()
 
     import torch
@@ -182,12 +185,70 @@ def main():
                            "kernel_GBps": round(nbytes / (ms["kernel"] * 1e-3) / 1e9, 1), "equal_to_torch": bool(same)}
     assert int(store.errors.item()) == 0
 
+    # ---- 4. loss head ----------------------------------------------------------------------------
+    # the store as a rollout leaves it (the timing loops above ended on record_only, whose masks do not
+    # belong to the recorded actions)
+    from splendor_gym.policy import masked_categorical
+    graphs["recorded"].replay()
+    store.compute_gae(last_value, gamma, lam)
+    clip_coef, vclip, vf_coef, ent_coef = 0.2, 0.2, 0.5, 0.03
+    loss_head = {}
+    for B in (256, 65536):
+        idx = torch.randperm(total, device=dev, generator=gen)[:B].contiguous()
+        mb = store.gather(idx)
+        with torch.no_grad():
+            logits0, value0 = agent.actor(mb["obs"]), agent.critic(mb["obs"])
+        leaves = {arm: (logits0.clone().requires_grad_(), value0.clone().requires_grad_()) for arm in ("kernel", "torch")}
+
+        def torch_head():
+            logits, value = leaves["torch"]
+            logits.grad = value.grad = None
+            probs = masked_categorical(logits, mb["mask"])
+            new_logprob, entropy = probs.log_prob(mb["action"]), probs.entropy().mean()
+            ratio = (new_logprob - mb["logprob"]).exp()
+            clip_adv = torch.clamp(ratio, 1 - clip_coef, 1 + clip_coef) * mb["adv"]
+            policy_loss = -torch.min(ratio * mb["adv"], clip_adv).mean()
+            v_pred = value.squeeze(-1)
+            v_clipped = mb["value"] + torch.clamp(v_pred - mb["value"], -vclip, vclip)
+            value_loss = 0.5 * torch.max((v_pred - mb["ret"]).pow(2), (v_clipped - mb["ret"]).pow(2)).mean()
+            (policy_loss + vf_coef * value_loss + ent_coef * entropy).backward()
+
+        def kernel_head():
+            logits, value = leaves["kernel"]
+            logits.grad = value.grad = None
+            store.loss(idx, logits, value, clip_coef, vclip, vf_coef, ent_coef)[0].backward()
+
+        def launches_only():  # spl_ppo_loss's two launches, without autograd's copies of the gradients
+            store.loss(idx, logits0, value0, clip_coef, vclip, vf_coef, ent_coef)
+
+        ms = timed({"kernel": kernel_head, "torch": torch_head, "launches": launches_only}, inner=200 if B <= 4096 else 20)
+        bad = int(store.loss(idx, logits0, value0)[1].bad)
+        scale = float(leaves["torch"][0].grad.abs().max())
+        diff = max(float((leaves["kernel"][0].grad - leaves["torch"][0].grad).abs().max()),
+                   float((leaves["kernel"][1].grad - leaves["torch"][1].grad).abs().max()))
+        # idx, mask word, action, four float planes, logits and value in; both gradients out; the partial sums
+        nbytes = B * (8 + 8 + 4 + 4 * 4 + 45 * 4 + 4 + 45 * 4 + 4) + 2 * 48 * ((B + 255) // 256) + 56
+        loss_head[f"B{B}"] = {"kernel_fwd_bwd_us": round(ms["kernel"] * 1e3, 1), "torch_fwd_bwd_us": round(ms["torch"] * 1e3, 1),
+                              "ratio_torch_over_kernel": round(ms["torch"] / ms["kernel"], 2),
+                              "launches_only_us": round(ms["launches"] * 1e3, 1), "bytes": nbytes,
+                              "launches_only_GBps": round(nbytes / (ms["launches"] * 1e-3) / 1e9, 1),
+                              "launches_only_fraction_of_8TBps": round(nbytes / (ms["launches"] * 1e-3) / 8e12, 4),
+                              "bad_rows": bad, "max_abs_gradient_difference_to_torch": diff, "max_abs_gradient": scale}
+    loss_head["note"] = ("forward and backward of the loss head from leaf logits / value tensors, fp32: PPORolloutStore.loss "
+                         "(spl_ppo_loss, then autograd's grad_output * gradient) beside the torch expression of ppo_update; "
+                         "launches_only: spl_ppo_loss alone")
+    if args.loss_json:
+        with open(args.loss_json, "w") as f:
+            json.dump({"metric": f"PPO loss head, store of {T} tables x {K} steps, one MI355X", "repeats": args.repeats,
+                       "loss": loss_head}, f, indent=1)
+            f.write("\n")
+
     print(json.dumps({"metric": f"PPO rollout store, {T} tables x {K} steps, one MI355X", "tables": T, "steps": K,
                       "repeats": args.repeats, "timing": "device events around back-to-back eager calls (graphs: one replay), arms alternating, medians; "
                                 "calls of a few microseconds are bound by the host's launch path",
                       "store_bytes": sum(getattr(store, n).numel() * getattr(store, n).element_size() for n in
                                          ("obs_u8", "mask_bits", "action", "logprob", "value", "reward", "done", "adv", "ret")),
-                      "record": rec, "gae": gae, "gather": gather}))
+                      "record": rec, "gae": gae, "gather": gather, "loss": loss_head}))
     env.close()
 
 
