@@ -1,5 +1,6 @@
 /*
- * splendor_ppo.h — C-ABI of the PPO rollout store (gfx950): record, GAE, minibatch gather and loss head.
+ * splendor_ppo.h — C-ABI of the PPO rollout store (gfx950): record, GAE, minibatch gather, loss head
+ * and optimiser step.
  *
  * The reference's learner (ppo_splendor.py:287-325) appends per-step numpy copies to Python lists,
  * runs GAE as a numpy loop on the host and re-uploads everything for the update.  These entry points
@@ -15,6 +16,9 @@
  *   spl_ppo_loss     the loss head of the update (ppo_splendor.py:337-352) for one minibatch of flat
  *                    positions: the loss, its statistics and its gradients with respect to the actor's
  *                    logits and the critic's value, the recorded quantities read from the planes
+ *   spl_ppo_adam     the optimiser step behind the backward pass (ppo_splendor.py:354-361): the
+ *                    global-norm clip, torch.optim.Adam's step and the target-KL early stop, decided
+ *                    on the device so that the host never waits for a minibatch's KL
  *
  * The store is step-major [K][T] (K steps, T tables), every plane caller-owned device memory:
  *   obs_u8     uint8  [K][T][300]  the compact rows of spl_step_args_t.obs_u8 (bytes 0..296 the values
@@ -166,6 +170,76 @@ typedef struct {
                                      need to clear it                                                */
 } spl_ppo_loss_t;
 
+/* ---------------------------------------------------------------------------------------------
+ * spl_ppo_adam: clip_grad_norm_, torch.optim.Adam.step and the target-KL `break` of one minibatch as
+ * one call (SPL_PPO_ADAM advertises it; SPL_PPO_ABI is unchanged, nothing above moved).
+ *
+ * The device state block (232 bytes, 8-byte aligned).  The host writes the hyper-parameters with small
+ * asynchronous copies; nothing of them is a kernel argument, so a captured call follows them. */
+#define SPL_PPO_ADAM 1
+#define SPL_PPO_ADAM_MAX_TENSORS 16
+#define SPL_PPO_ADAM_CHUNK 2048 /* floats of one partial sum's chunk; a segment starts a new chunk */
+#define SPL_PPO_ADAM_PARTS 512  /* partial sums at the most: chunk c belongs to partial c % 512     */
+#define SPL_PPO_ADAM_EPOCH 0    /* spl_ppo_adam_begin: a new epoch                                  */
+#define SPL_PPO_ADAM_UPDATE 1   /* spl_ppo_adam_begin: a new update                                 */
+
+typedef struct {
+    double lr, beta1, beta2, eps;
+    double max_norm;             /* negative: no clipping                                            */
+    double target_kl;            /* <= 0: the gate is off                                            */
+    int64_t step;                /* applied steps since creation: drives the bias corrections        */
+    int64_t applied, gated, nonfinite; /* calls since the last begin(UPDATE): applied, skipped by the
+                                    latch, skipped for a non-finite norm                             */
+    int32_t stopped;             /* the gate's latch                                                 */
+    int32_t active;              /* the latest call: 1 applied, 0 skipped                            */
+    double grad_norm, clip_coef; /* of the latest call (clip_coef as the float32 the elements saw)   */
+    spl_ppo_loss_out_t first;    /* loss_out of the update's first applied call                      */
+    spl_ppo_loss_out_t last;     /* loss_out of the latest applied call                              */
+    int64_t step_in;             /* hand-off words of a call's two launches (below); not for callers */
+    int32_t armed, reserved;
+} spl_ppo_adam_state_t;
+
+/* One call, with g the gradients as stored, in this order:
+ *  1. norm = sqrt(SUM g*g) over all segments: each square one float32 multiply, the sum float64 in a
+ *     fixed order that depends on the segments' sizes alone (never on the device), so two calls on the
+ *     same bytes give the same bytes.  With cn = max_norm / (norm + 1e-6) in float64:
+ *       clip_coef = fp32(max_norm < 0 ? 1 : cn < 1 ? cn : 1)
+ *  2. The call is active when `stopped` was clear on entry and norm is finite.  A set latch skips the
+ *     call and counts in `gated` (whatever the norm); else a non-finite norm skips it and counts in
+ *     `nonfinite`.  A skipped call leaves every parameter, moment and `step` bit for bit as it was.
+ *  3. Active: step += 1, applied += 1; *loss_out (if given) is copied to `last`, and to `first` when
+ *     this is the first applied call since begin(UPDATE).
+ *  4. Whether active or not: if target_kl > 0 and a KL is given (*approx_kl, else loss_out->approx_kl)
+ *     and KL > target_kl, `stopped` is set.  The call whose KL crossed the line is itself applied, as
+ *     the reference steps before its `break`; the calls after it are gated until begin().
+ *  5. Active, per element, g' = g * clip_coef, every operation one float32 operation, none fused:
+ *       m = m + (g' - m) * fp32(1 - beta1)
+ *       v = v * fp32(beta2) + fp32(1 - beta2) * (g' * g')
+ *       p = p - fp32(lr / (1 - beta1^step)) * (m / (sqrt(v) / fp32(sqrt(1 - beta2^step)) + fp32(eps)))
+ *     the scalars computed in float64 from the state block and rounded once.  This is torch.optim.Adam
+ *     (_single_tensor_adam: no weight decay, no amsgrad, not maximising) behind clip_grad_norm_.
+ * Two launches.  The first writes each partial sum of squares, and its workgroup 0 alone reads the
+ * latch, leaves `armed` and `step_in` for the second and applies rule 4.  In the second every workgroup
+ * adds the partial sums in the same order, decides alike and applies the step; its workgroup 0 writes
+ * active, the counters, grad_norm, clip_coef and the latches, none of which that launch reads.  No
+ * launch writes a word that all its workgroups read, and there are no floating-point atomics. */
+typedef struct {
+    int32_t n;                   /* segments, 1..SPL_PPO_ADAM_MAX_TENSORS                            */
+    int32_t reserved;            /* 0                                                               */
+    float *param[SPL_PPO_ADAM_MAX_TENSORS];      /* [numel[i]] each, wherever it lies; 4-byte aligned */
+    const float *grad[SPL_PPO_ADAM_MAX_TENSORS]; /* [numel[i]]                                       */
+    int64_t numel[SPL_PPO_ADAM_MAX_TENSORS];     /* >= 1 each, at most 2^31 together                 */
+    float *exp_avg, *exp_avg_sq; /* the moment arenas: segment i at the sum over j < i of numel[j]
+                                    rounded up to a multiple of 4 floats.  A segment whose parameter,
+                                    gradient and two moment pointers are all 16-byte aligned moves 16
+                                    bytes a lane; any other gives the same bits, a dword at a time  */
+    spl_ppo_adam_state_t *state; /* device, 8-byte aligned                                           */
+    const double *approx_kl;     /* device, 8-byte aligned, or NULL                                  */
+    const spl_ppo_loss_out_t *loss_out; /* device, 8-byte aligned, or NULL                           */
+    void *scratch;               /* spl_ppo_adam_scratch_bytes(total) bytes, device, 8-byte aligned; no
+                                    need to clear it                                                 */
+} spl_ppo_adam_t;
+
 /* n rows of one step into the store */
 int spl_ppo_record(int32_t n, const spl_ppo_record_t *args, void *stream);
 /* bytes of spl_ppo_gae_t.scratch for T tables (SPL_E_ARG for T < 1) */
@@ -180,6 +254,15 @@ int64_t spl_ppo_loss_scratch_bytes(int32_t B);
 /* loss, statistics and gradients of one minibatch of B rows: two launches (the rows with each
  * workgroup's partial sums, then a one-workgroup finish), asynchronous on `stream`, nothing allocated */
 int spl_ppo_loss(int32_t B, const spl_ppo_loss_t *args, void *stream);
+/* bytes of spl_ppo_adam_t.scratch for segments of total_numel floats together (SPL_E_ARG below 1 or
+ * above 2^31): room for a partial sum per chunk had every segment but one a single element */
+int64_t spl_ppo_adam_scratch_bytes(int64_t total_numel);
+/* SPL_PPO_ADAM_EPOCH clears `stopped`; SPL_PPO_ADAM_UPDATE clears `stopped`, `applied`, `gated`,
+ * `nonfinite` and `first`.  One launch, asynchronous on `stream` */
+int spl_ppo_adam_begin(spl_ppo_adam_state_t *state, int32_t what, void *stream);
+/* norm clip, Adam step and KL gate of one minibatch: two launches, asynchronous on `stream`, nothing
+ * allocated */
+int spl_ppo_adam(const spl_ppo_adam_t *args, void *stream);
 
 #ifdef __cplusplus
 }

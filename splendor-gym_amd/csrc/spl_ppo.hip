@@ -1,7 +1,8 @@
 // spl_ppo.hip — the PPO rollout store (include/splendor_ppo.h): record one step's rows, the GAE
 // reverse scan of ppo_splendor.py:304-314 with the advantage statistics of :325, and the minibatch
 // gather that expands the compact rows into ActorCritic.get_action_and_value's inputs, and the loss head
-// of the update (loss, statistics and the gradients with respect to the logits and the value).
+// of the update (loss, statistics and the gradients with respect to the logits and the value), and the
+// optimiser step behind the backward pass (global-norm clip, Adam, target-KL gate).
 //
 // The GAE scan must be bit-equal to numpy, which never fuses a multiply with an add, while HIP device
 // code contracts a*b+c into an FMA by default.  Contraction is switched off for this whole file by
@@ -451,6 +452,187 @@ __global__ __launch_bounds__(kBlock) void k_loss_finish(int blocks, int B, float
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// adam
+// ---------------------------------------------------------------------------------------------
+// The segments are cut into chunks of kChunk floats (a segment starts a new chunk), a workgroup takes
+// chunks blockIdx.x, blockIdx.x + kParts, ... and thread t of it the 16-byte pieces t and t + 256 of each:
+// wave instructions of 1 KiB when the segment is 16-byte aligned throughout, the same elements a dword at
+// a time when it is not.  Both launches walk the chunks alike.  The agent's 295 982 floats are 150 chunks:
+// 8 MB through L2 in two launches, so the call is bound by its launches, not by the memory behind them.
+constexpr int kChunk = SPL_PPO_ADAM_CHUNK, kParts = SPL_PPO_ADAM_PARTS, kSegs = SPL_PPO_ADAM_MAX_TENSORS;
+constexpr int kPieces = kChunk / 4 / kBlock;  // 16-byte pieces of a chunk per thread
+static_assert(kPieces * 4 * kBlock == kChunk, "a chunk is a whole number of 16-byte pieces per thread");
+
+struct Adam {
+    float *p[kSegs];
+    const float *g[kSegs];
+    int64_t numel[kSegs];
+    int64_t at[kSegs];          // the segment's first float in the arenas
+    int32_t chunk0[kSegs + 1];  // the segment's first chunk; chunk0[n] = all chunks
+    int32_t n;
+    uint32_t wide;              // bit i: segment i moves 16 bytes a lane
+    float *m, *v;
+    spl_ppo_adam_state_t *st;
+    const double *kl;
+    const spl_ppo_loss_out_t *lo;
+    double *partial;
+};
+
+// floats e .. e + 3 of a segment of `numel` floats (e < numel; past the end: 0)
+__device__ __forceinline__ void load4(const float *src, int64_t e, int64_t numel, bool wide, float (&x)[4]) {
+    if (wide && e + 4 <= numel) {
+        const float4 q = *reinterpret_cast<const float4 *>(src + e);
+        x[0] = q.x, x[1] = q.y, x[2] = q.z, x[3] = q.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) x[j] = e + j < numel ? src[e + j] : 0.f;
+    }
+}
+
+__device__ __forceinline__ void store4(float *dst, int64_t e, int64_t numel, bool wide, const float (&x)[4]) {
+    if (wide && e + 4 <= numel) {
+        *reinterpret_cast<float4 *>(dst + e) = make_float4(x[0], x[1], x[2], x[3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (e + j < numel) dst[e + j] = x[j];
+    }
+}
+
+// the segment of chunk c (uniform over the workgroup)
+__device__ __forceinline__ int segment_of(const Adam &a, int c) {
+    int s = 0;
+    while (s + 1 < a.n && c >= a.chunk0[s + 1]) ++s;
+    return s;
+}
+
+// Launch 1.  partial[b] = the squares of chunks b, b + kParts, ...: per thread in element order, then
+// block_sum's tree.  Thread 0 of workgroup 0 is the only reader of the latch and the only writer of the
+// words launch 2's workgroups all read.
+__global__ __launch_bounds__(kBlock) void k_adam_norm(Adam a) {
+    __shared__ double lds[kBlock];
+    const int chunks = a.chunk0[a.n];
+    double acc = 0.0;
+    for (int c = blockIdx.x; c < chunks; c += kParts) {
+        const int s = segment_of(a, c);
+        const int64_t numel = a.numel[s], base = (int64_t)(c - a.chunk0[s]) * kChunk;
+        const float *g = a.g[s];
+        const bool wide = (a.wide >> s) & 1;
+#pragma unroll
+        for (int k = 0; k < kPieces; ++k) {
+            const int64_t e = base + 4 * (int64_t)(threadIdx.x + k * kBlock);
+            if (e < numel) {
+                float x[4];
+                load4(g, e, numel, wide, x);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float sq = x[j] * x[j];
+                    acc += (double)sq;
+                }
+            }
+        }
+    }
+    const double sum = block_sum(acc, lds);
+    if (threadIdx.x == 0) {
+        a.partial[blockIdx.x] = sum;
+        if (blockIdx.x == 0) {
+            spl_ppo_adam_state_t *st = a.st;
+            st->armed = st->stopped ? 0 : 1;
+            st->step_in = st->step;
+            const double target = st->target_kl;
+            if (target > 0.0 && (a.kl || a.lo)) {
+                const double kl = a.kl ? *a.kl : a.lo->approx_kl;
+                if (kl > target) st->stopped = 1;
+            }
+        }
+    }
+}
+
+struct AdamScalars {
+    float coef, w1, b2, w2, step_size, bc2_sqrt, eps;
+    int active;
+};
+
+// Launch 2.  Every workgroup adds the partial sums in one order (lane j takes j, j + 256, ..., then
+// block_sum's tree), so all decide alike; workgroup 0 writes the outcome to words this launch never reads.
+__global__ __launch_bounds__(kBlock) void k_adam_step(Adam a, int parts) {
+    __shared__ double lds[kBlock];
+    __shared__ AdamScalars shared;
+    double acc = 0.0;
+    for (int p = threadIdx.x; p < parts; p += kBlock) acc += a.partial[p];
+    const double sumsq = block_sum(acc, lds);
+    if (threadIdx.x == 0) {
+        spl_ppo_adam_state_t *st = a.st;
+        const double norm = sqrt(sumsq);
+        const bool finite = norm - norm == 0.0;
+        const bool armed = st->armed != 0, active = armed && finite;
+        const double mx = st->max_norm, cn = mx / (norm + 1e-6);
+        const float coef = mx < 0.0 ? 1.f : (float)(cn < 1.0 ? cn : 1.0);
+        const double step = (double)(st->step_in + 1), b1 = st->beta1, b2 = st->beta2;
+        const double bc1 = 1.0 - pow(b1, step), bc2 = 1.0 - pow(b2, step);
+        shared = AdamScalars{coef, (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)(st->lr / bc1),
+                             (float)sqrt(bc2), (float)st->eps, active ? 1 : 0};
+        if (blockIdx.x == 0) {
+            st->active = active ? 1 : 0;
+            st->grad_norm = norm;
+            st->clip_coef = (double)coef;
+            if (!armed) {
+                st->gated += 1;
+            } else if (!finite) {
+                st->nonfinite += 1;
+            } else {
+                st->step = st->step_in + 1;
+                if (a.lo) {
+                    st->last = *a.lo;
+                    if (st->applied == 0) st->first = *a.lo;
+                }
+                st->applied += 1;
+            }
+        }
+    }
+    __syncthreads();
+    const AdamScalars sc = shared;
+    if (!sc.active) return;
+    const int chunks = a.chunk0[a.n];
+    for (int c = blockIdx.x; c < chunks; c += kParts) {
+        const int s = segment_of(a, c);
+        const int64_t numel = a.numel[s], base = (int64_t)(c - a.chunk0[s]) * kChunk;
+        float *p = a.p[s], *m = a.m + a.at[s], *v = a.v + a.at[s];
+        const float *g = a.g[s];
+        const bool wide = (a.wide >> s) & 1;
+#pragma unroll
+        for (int k = 0; k < kPieces; ++k) {
+            const int64_t e = base + 4 * (int64_t)(threadIdx.x + k * kBlock);
+            if (e < numel) {
+                float xp[4], xg[4], xm[4], xv[4];
+                load4(p, e, numel, wide, xp);
+                load4(g, e, numel, wide, xg);
+                load4(m, e, numel, wide, xm);
+                load4(v, e, numel, wide, xv);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float gc = xg[j] * sc.coef;
+                    xm[j] = xm[j] + (gc - xm[j]) * sc.w1;
+                    xv[j] = xv[j] * sc.b2 + sc.w2 * (gc * gc);
+                    xp[j] = xp[j] - sc.step_size * (xm[j] / (sqrtf(xv[j]) / sc.bc2_sqrt + sc.eps));
+                }
+                store4(p, e, numel, wide, xp);
+                store4(m, e, numel, wide, xm);
+                store4(v, e, numel, wide, xv);
+            }
+        }
+    }
+}
+
+__global__ void k_adam_begin(spl_ppo_adam_state_t *st, int update) {
+    st->stopped = 0;
+    if (update) {
+        st->applied = st->gated = st->nonfinite = 0;
+        st->first = spl_ppo_loss_out_t{};
+    }
+}
+
 }  // namespace splp
 
 using namespace splp;
@@ -563,6 +745,69 @@ int spl_ppo_loss(int32_t B, const spl_ppo_loss_t *a, void *stream) {
     hipLaunchKernelGGL(k_loss, dim3(blocks), dim3(kBlock), 0, s, B, (int64_t)a->K * a->T, 1.f / (float)B, *a, partial);
     hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(kBlock), 0, s, blocks, B, a->vf_coef, a->ent_coef, partial, a->out);
     return spl_launched("k_loss");
+}
+
+static int64_t adam_chunks(int64_t numel) { return (numel + kChunk - 1) / kChunk; }
+
+int64_t spl_ppo_adam_scratch_bytes(int64_t total_numel) {
+    if (total_numel < 1) return spl_fail(SPL_E_ARG, "total_numel must be positive");
+    if (total_numel > (int64_t)1 << 31) return spl_fail(SPL_E_ARG, "total_numel must not exceed 2^31");
+    const int64_t chunks = adam_chunks(total_numel) + (kSegs - 1);
+    return (chunks < kParts ? chunks : kParts) * (int64_t)sizeof(double);
+}
+
+int spl_ppo_adam_begin(spl_ppo_adam_state_t *state, int32_t what, void *stream) {
+    if (!state) return spl_fail(SPL_E_ARG, "null state");
+    if (spl_misaligned(state, 8)) return spl_fail(SPL_E_ARG, "state must be 8-byte aligned");
+    if (what != SPL_PPO_ADAM_EPOCH && what != SPL_PPO_ADAM_UPDATE)
+        return spl_fail(SPL_E_ARG, "what must be SPL_PPO_ADAM_EPOCH or SPL_PPO_ADAM_UPDATE");
+    hipLaunchKernelGGL(k_adam_begin, dim3(1), dim3(1), 0, (hipStream_t)stream, state, what == SPL_PPO_ADAM_UPDATE ? 1 : 0);
+    return spl_launched("k_adam_begin");
+}
+
+int spl_ppo_adam(const spl_ppo_adam_t *a, void *stream) {
+    if (!a) return spl_fail(SPL_E_ARG, "null adam arguments");
+    if (a->n < 1 || a->n > kSegs) return spl_fail(SPL_E_ARG, "n must be in 1..SPL_PPO_ADAM_MAX_TENSORS");
+    if (a->reserved != 0) return spl_fail(SPL_E_ARG, "reserved must be 0");
+    if (!a->exp_avg || !a->exp_avg_sq || !a->state || !a->scratch) return spl_fail(SPL_E_ARG, "null buffer");
+    if (spl_misaligned(a->exp_avg, 4) || spl_misaligned(a->exp_avg_sq, 4))
+        return spl_fail(SPL_E_ARG, "the moment arenas must be 4-byte aligned");
+    if (spl_misaligned(a->state, 8) || spl_misaligned(a->scratch, 8) || spl_misaligned(a->approx_kl, 8) ||
+        spl_misaligned(a->loss_out, 8))
+        return spl_fail(SPL_E_ARG, "state, scratch, approx_kl and loss_out must be 8-byte aligned");
+    Adam k{};
+    int64_t total = 0, at = 0, chunks = 0;
+    for (int i = 0; i < a->n; ++i) {
+        if (!a->param[i] || !a->grad[i]) return spl_fail(SPL_E_ARG, "null buffer: a segment needs its parameter and its gradient");
+        if (spl_misaligned(a->param[i], 4) || spl_misaligned(a->grad[i], 4))
+            return spl_fail(SPL_E_ARG, "parameters and gradients must be 4-byte aligned");
+        if (a->numel[i] < 1) return spl_fail(SPL_E_ARG, "numel must be positive");
+        if (a->numel[i] > ((int64_t)1 << 31) - total) return spl_fail(SPL_E_ARG, "the segments together must not exceed 2^31 floats");
+        total += a->numel[i];
+        k.p[i] = a->param[i];
+        k.g[i] = a->grad[i];
+        k.numel[i] = a->numel[i];
+        k.at[i] = at;
+        k.chunk0[i] = (int32_t)chunks;
+        if (!spl_misaligned(a->param[i], 16) && !spl_misaligned(a->grad[i], 16) && !spl_misaligned(a->exp_avg + at, 16) &&
+            !spl_misaligned(a->exp_avg_sq + at, 16))
+            k.wide |= 1u << i;
+        at += (a->numel[i] + 3) / 4 * 4;
+        chunks += adam_chunks(a->numel[i]);
+    }
+    k.chunk0[a->n] = (int32_t)chunks;
+    k.n = a->n;
+    k.m = a->exp_avg;
+    k.v = a->exp_avg_sq;
+    k.st = a->state;
+    k.kl = a->approx_kl;
+    k.lo = a->loss_out;
+    k.partial = static_cast<double *>(a->scratch);
+    const int parts = (int)(chunks < kParts ? chunks : kParts);  // <= spl_ppo_adam_scratch_bytes(total) / 8
+    const hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_adam_norm, dim3(parts), dim3(kBlock), 0, s, k);
+    hipLaunchKernelGGL(k_adam_step, dim3(parts), dim3(kBlock), 0, s, k, parts);
+    return spl_launched("k_adam");
 }
 
 }  // extern "C"

@@ -119,6 +119,25 @@ class PpoLoss(ctypes.Structure):
                [(k, c_void_p) for k in ("dlogits", "dvalue", "out", "errors", "scratch")]
 
 
+PPO_ADAM_MAX_TENSORS, PPO_ADAM_CHUNK, PPO_ADAM_PARTS = 16, 2048, 512  # SPL_PPO_ADAM_*
+PPO_ADAM_EPOCH, PPO_ADAM_UPDATE = 0, 1
+
+
+class PpoAdamState(ctypes.Structure):
+    """spl_ppo_adam_state_t (include/splendor_ppo.h)"""
+    _fields_ = [(k, ctypes.c_double) for k in ("lr", "beta1", "beta2", "eps", "max_norm", "target_kl")] + \
+               [(k, c_int64) for k in ("step", "applied", "gated", "nonfinite")] + \
+               [("stopped", c_int32), ("active", c_int32), ("grad_norm", ctypes.c_double), ("clip_coef", ctypes.c_double),
+                ("first", PpoLossOut), ("last", PpoLossOut), ("step_in", c_int64), ("armed", c_int32), ("reserved", c_int32)]
+
+
+class PpoAdam(ctypes.Structure):
+    """spl_ppo_adam_t (include/splendor_ppo.h)"""
+    _fields_ = [("n", c_int32), ("reserved", c_int32), ("param", c_void_p * PPO_ADAM_MAX_TENSORS),
+                ("grad", c_void_p * PPO_ADAM_MAX_TENSORS), ("numel", c_int64 * PPO_ADAM_MAX_TENSORS)] + \
+               [(k, c_void_p) for k in ("exp_avg", "exp_avg_sq", "state", "approx_kl", "loss_out", "scratch")]
+
+
 EVAL_ABI = 1                       # SPL_EVAL_ABI (include/splendor_eval.h)
 POLICY_GREEDY_V2, EVAL_KEEP = 3, -1  # SPL_POLICY_GREEDY_V2, SPL_EVAL_KEEP: spl_eval_scripted_act only
 EVAL_COLS = 8                      # wins, losses, draws, unfinished, sum turns, sum prestige, checks, illegal
@@ -219,6 +238,9 @@ SIGNATURES = {
     "spl_ppo_gather": ([c_int32, ctypes.POINTER(PpoGather), c_void_p], c_int32),
     "spl_ppo_loss_scratch_bytes": ([c_int32], c_int64),
     "spl_ppo_loss": ([c_int32, ctypes.POINTER(PpoLoss), c_void_p], c_int32),
+    "spl_ppo_adam_scratch_bytes": ([c_int64], c_int64),
+    "spl_ppo_adam_begin": ([c_void_p, c_int32, c_void_p], c_int32),
+    "spl_ppo_adam": ([ctypes.POINTER(PpoAdam), c_void_p], c_int32),
     # include/splendor_eval.h
     "spl_eval_abi_version": ([], c_int32),
     "spl_eval_scripted_act": ([c_int32, ctypes.POINTER(EvalAct), c_void_p], c_int32),

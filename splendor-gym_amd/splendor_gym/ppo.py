@@ -14,7 +14,10 @@ masks: 2.8 GB instead of 10.4 GB at 128 steps x 65 536 tables):
     rows, DualStepVectorEnv.dual_step), recorded, and the bootstrap value; eager or one hipGraph;
   * ``ppo_update``  the update of ppo_splendor.py:327-361 in torch over ``store.minibatches``; with
     ``fused_loss=True`` its loss head (masked softmax, ratio, clips, means, and their gradients) is
-    ``PPORolloutStore.loss``, one device call on the store's planes.
+    ``PPORolloutStore.loss``, one device call on the store's planes;
+  * ``DeviceAdam``  what follows loss.backward() as one device call per minibatch (spl_ppo_adam): the
+    global-norm clip, torch.optim.Adam's step and the target-KL early stop, decided on the device, so that
+    ``ppo_update`` with it reads the device once per update instead of once per minibatch.
 
 The two networks' forward and backward passes stay in torch.  There is no CPU fallback.
 """
@@ -310,6 +313,213 @@ def collect(env, agent_k, store, obs, mask, seed=0, table0=0, graph=False):
         return out
 
 
+def adam_state_dict(template, step, exp_avg, exp_avg_sq):
+    """torch.optim.Adam's state_dict for moments kept elsewhere: `template` is the state_dict of a fresh
+    torch.optim.Adam over the same parameters (it supplies param_groups with the installed torch's keys),
+    exp_avg / exp_avg_sq one tensor per parameter, step the number of steps taken.  Like torch, no step
+    taken means no per-parameter state."""
+    import torch
+    state = {}
+    if step > 0:
+        for i, (m, v) in enumerate(zip(exp_avg, exp_avg_sq)):
+            state[i] = {"step": torch.tensor(float(step), dtype=torch.float32), "exp_avg": m.clone(), "exp_avg_sq": v.clone()}
+    return {"state": state, "param_groups": template["param_groups"]}
+
+
+def adam_state_of(state_dict, shapes):
+    """The reverse of adam_state_dict for parameters of `shapes`: (step, exp_avg list, exp_avg_sq list,
+    param group).  ValueError for anything DeviceAdam does not do (several groups, weight decay, amsgrad,
+    maximize), for moments of another shape and for parameters that disagree about the step; a parameter
+    without state has taken no step."""
+    groups = state_dict["param_groups"]
+    if len(groups) != 1:
+        raise ValueError("DeviceAdam holds one parameter group")
+    g = groups[0]
+    if g.get("weight_decay", 0) != 0 or g.get("amsgrad", False) or g.get("maximize", False):
+        raise ValueError("DeviceAdam has no weight decay, no amsgrad and does not maximise")
+    if list(g["params"]) != list(range(len(shapes))):
+        raise ValueError(f"the state_dict is for {len(g['params'])} parameters, not {len(shapes)}")
+    state = state_dict["state"]
+    steps = {int(float(state[i]["step"])) if i in state else 0 for i in range(len(shapes))}
+    if len(steps) != 1:
+        raise ValueError(f"the parameters disagree about the step: {sorted(steps)}")
+    ms, vs = [], []
+    for i, shape in enumerate(shapes):
+        m, v = (state[i]["exp_avg"], state[i]["exp_avg_sq"]) if i in state else (None, None)
+        for x in (m, v):
+            if x is not None and tuple(x.shape) != tuple(shape):
+                raise ValueError(f"parameter {i}: moments of shape {tuple(x.shape)} for a parameter of shape {tuple(shape)}")
+        ms.append(m)
+        vs.append(v)
+    return steps.pop(), ms, vs, g
+
+
+class DeviceAdam:
+    """clip_grad_norm_, torch.optim.Adam.step and the target-KL early stop as one device call per minibatch
+    (spl_ppo_adam, include/splendor_ppo.h).  The parameters and their gradients stay where torch put them;
+    the two moments live in arenas this object owns, and the hyper-parameters, the step count, the gate's
+    latch and the counters in a small state block on the device, so nothing here waits for the device
+    except read_state(), state_dict() and load_state_dict().
+
+    params: at most 16 contiguous float32 tensors on one GPU (ValueError otherwise).  max_grad_norm None
+    or negative: no clipping.  target_kl <= 0: no gate.  With a gate, a step whose KL exceeds target_kl is
+    applied and the steps after it are skipped (and counted in `gated`) until begin_epoch() or
+    begin_update(), which is the reference's `break` without the host reading the KL."""
+
+    def __init__(self, params, lr=2.5e-4, betas=(0.9, 0.999), eps=1e-5, max_grad_norm=0.5, target_kl=0.0):
+        torch = _native.require_gpu()
+        self.torch, self.lib = torch, _native.load_library()
+        self.params = list(params)
+        if not 1 <= len(self.params) <= _native.PPO_ADAM_MAX_TENSORS:
+            raise ValueError(f"DeviceAdam takes 1 to {_native.PPO_ADAM_MAX_TENSORS} parameter tensors, not {len(self.params)}")
+        self.device = self.params[0].device if isinstance(self.params[0], torch.Tensor) else None
+        for i, p in enumerate(self.params):
+            if not isinstance(p, torch.Tensor) or p.dtype != torch.float32 or not p.is_contiguous() or p.numel() < 1 or \
+                    p.device != self.device or p.device.type != "cuda":
+                raise ValueError(f"parameter {i} must be a non-empty contiguous float32 tensor on one GPU (no CPU fallback)")
+        self._at, total = [], 0
+        for p in self.params:
+            self._at.append(total)
+            total += (p.numel() + 3) // 4 * 4
+        self.numel = sum(p.numel() for p in self.params)
+        self.arena_floats = total
+        scratch = int(check(self.lib, self.lib.spl_ppo_adam_scratch_bytes(self.numel)))
+        self._scratch = torch.empty(scratch // 8, dtype=torch.float64, device=self.device)
+        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        self.max_grad_norm = -1.0 if max_grad_norm is None else float(max_grad_norm)
+        self.target_kl = float(target_kl)
+        host = _native.PpoAdamState(lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
+                                    max_norm=self.max_grad_norm, target_kl=self.target_kl)
+        self._state = torch.frombuffer(bytearray(bytes(host)), dtype=torch.float64).to(self.device)
+        self._state_i64 = self._state.view(torch.int64)
+        a = _native.PpoAdam(n=len(self.params), reserved=0, state=self._state.data_ptr(), scratch=self._scratch.data_ptr())
+        for i, p in enumerate(self.params):
+            a.numel[i] = p.numel()
+        self._args = a
+        self._place_arenas(torch.zeros(total, dtype=torch.float32, device=self.device),
+                           torch.zeros(total, dtype=torch.float32, device=self.device))
+
+    def _place_arenas(self, exp_avg, exp_avg_sq):
+        """The two moment arenas: contiguous float32 [arena_floats] on the device, segment i at the sum of the
+        earlier segments' sizes, each rounded up to a multiple of 4."""
+        for x in (exp_avg, exp_avg_sq):
+            if x.dtype != self.torch.float32 or tuple(x.shape) != (self.arena_floats,) or not x.is_contiguous() or \
+                    x.device != self.device:
+                raise ValueError(f"an arena must be a contiguous float32 [{self.arena_floats}] tensor on {self.device}")
+        self._exp_avg, self._exp_avg_sq = exp_avg, exp_avg_sq
+        self._args.exp_avg, self._args.exp_avg_sq = exp_avg.data_ptr(), exp_avg_sq.data_ptr()
+
+    def _stream(self):
+        return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _set(self, field, value, integer=False):
+        """One asynchronous small write into the state block (a captured step() reads the block, so it
+        follows the write)."""
+        word = getattr(_native.PpoAdamState, field).offset // 8
+        (self._state_i64 if integer else self._state)[word:word + 1].fill_(value)
+
+    def set_lr(self, lr):
+        self.lr = float(lr)
+        self._set("lr", self.lr)
+
+    def set_betas(self, betas):
+        self.betas = (float(betas[0]), float(betas[1]))
+        self._set("beta1", self.betas[0])
+        self._set("beta2", self.betas[1])
+
+    def set_eps(self, eps):
+        self.eps = float(eps)
+        self._set("eps", self.eps)
+
+    def set_max_grad_norm(self, max_grad_norm):
+        self.max_grad_norm = -1.0 if max_grad_norm is None else float(max_grad_norm)
+        self._set("max_norm", self.max_grad_norm)
+
+    def set_target_kl(self, target_kl):
+        self.target_kl = float(target_kl)
+        self._set("target_kl", self.target_kl)
+
+    def _begin(self, what):
+        with self.torch.cuda.device(self.device):
+            check(self.lib, self.lib.spl_ppo_adam_begin(self._state.data_ptr(), what, self._stream()))
+
+    def begin_update(self):
+        """A new update: re-arms the gate and clears applied, gated, nonfinite and `first` (asynchronous)."""
+        self._begin(_native.PPO_ADAM_UPDATE)
+
+    def begin_epoch(self):
+        """A new epoch: re-arms the gate (asynchronous)."""
+        self._begin(_native.PPO_ADAM_EPOCH)
+
+    def step(self, loss_out=None, approx_kl=None):
+        """One call on the current stream with every p.grad as it stands, then p.grad = None: gradients are
+        taken, never accumulated into, so there is no zero_grad launch.  approx_kl: this minibatch's KL for
+        the gate, a one-element float64 (or float32, converted) tensor on the device; default:
+        loss_out.approx_kl.  loss_out: a PPOLossOut to latch into `first` / `last` when the step is applied.
+        A missing, non-contiguous or non-float32 gradient raises before anything is launched."""
+        t, a = self.torch, self._args
+        for i, p in enumerate(self.params):
+            g = p.grad
+            if g is None:
+                raise ValueError(f"parameter {i} has no gradient")
+            if g.dtype != t.float32 or not g.is_contiguous() or g.shape != p.shape or g.device != self.device:
+                raise ValueError(f"the gradient of parameter {i} must be a contiguous float32 tensor of its shape on {self.device}")
+            a.param[i], a.grad[i] = p.data_ptr(), g.data_ptr()
+        if approx_kl is not None:
+            if not isinstance(approx_kl, t.Tensor) or approx_kl.numel() != 1 or approx_kl.device != self.device or \
+                    approx_kl.dtype not in (t.float32, t.float64):
+                raise ValueError(f"approx_kl must be a one-element float64 or float32 tensor on {self.device}")
+            approx_kl = approx_kl.detach().to(t.float64).contiguous()
+        if loss_out is not None and (not isinstance(loss_out, PPOLossOut) or loss_out.buf.device != self.device):
+            raise ValueError(f"loss_out must be a PPOLossOut on {self.device}")
+        a.approx_kl = None if approx_kl is None else approx_kl.data_ptr()
+        a.loss_out = None if loss_out is None else loss_out.buf.data_ptr()
+        with t.cuda.device(self.device):
+            check(self.lib, self.lib.spl_ppo_adam(ctypes.byref(a), self._stream()))
+        for p in self.params:
+            p.grad = None
+
+    def read_state(self):
+        """The state block as Python numbers (one synchronising read): step, applied, gated, nonfinite,
+        stopped, active, grad_norm, clip_coef, the hyper-parameters as the device holds them, and first /
+        last as dictionaries of loss, policy_loss, value_loss, entropy, approx_kl, clipfrac and bad."""
+        s = _native.PpoAdamState.from_buffer_copy(self._state.cpu().numpy().tobytes())
+        latch = lambda o: {**{k: float(getattr(o, k)) for k in PPOLossOut.STATS}, "bad": int(o.bad)}
+        res = {k: int(getattr(s, k)) for k in ("step", "applied", "gated", "nonfinite", "stopped", "active")}
+        res.update({k: float(getattr(s, k)) for k in ("grad_norm", "clip_coef", "lr", "beta1", "beta2", "eps", "max_norm", "target_kl")})
+        return {**res, "first": latch(s.first), "last": latch(s.last)}
+
+    def _moments(self, arena):
+        return [arena[at:at + p.numel()].view(p.shape) for at, p in zip(self._at, self.params)]
+
+    def _template(self):
+        t = self.torch
+        shells = [t.nn.Parameter(t.empty(0)) for _ in self.params]
+        return t.optim.Adam(shells, lr=self.lr, betas=self.betas, eps=self.eps).state_dict()
+
+    def state_dict(self):
+        """torch.optim.Adam's own format (state[i] = {step, exp_avg, exp_avg_sq}, param_groups), so that a
+        run can move between the two optimisers.  max_grad_norm and target_kl are not part of it.
+        Synchronises."""
+        step = int(self._state_i64[_native.PpoAdamState.step.offset // 8].item())
+        return adam_state_dict(self._template(), step, self._moments(self._exp_avg), self._moments(self._exp_avg_sq))
+
+    def load_state_dict(self, state_dict):
+        """Takes a torch.optim.Adam (or DeviceAdam) state_dict for the same parameters: the moments, the step
+        and the group's lr, betas and eps."""
+        step, ms, vs, group = adam_state_of(state_dict, [p.shape for p in self.params])
+        for arena, src in ((self._exp_avg, ms), (self._exp_avg_sq, vs)):
+            for dst, x in zip(self._moments(arena), src):
+                if x is None:
+                    dst.zero_()
+                else:
+                    dst.copy_(x.to(device=self.device, dtype=self.torch.float32))
+        self._set("step", step, integer=True)
+        self.set_lr(group["lr"])
+        self.set_betas(group["betas"])
+        self.set_eps(group["eps"])
+
+
 def ppo_update(agent, optimizer, store, clip_coef=0.2, vclip=0.2, ent_coef=0.03, vf_coef=0.5, update_epochs=4,
                minibatch_size=256, target_kl=0.02, max_grad_norm=0.5, generator=None, entropy_bonus=False,
                fused_loss=False):
@@ -327,8 +537,21 @@ def ppo_update(agent, optimizer, store, clip_coef=0.2, vclip=0.2, ent_coef=0.03,
 
     Returns the last minibatch's policy_loss, value_loss, entropy and approx_kl, first_approx_kl (the
     first minibatch's, evaluated before any optimiser step) and the number of optimiser steps; with
-    fused_loss also the last minibatch's clipfrac."""
+    fused_loss also the last minibatch's clipfrac.
+
+    optimizer may be a DeviceAdam.  Then the norm clip, the Adam step and the early stop are one device call
+    per minibatch (DeviceAdam.step, fed the minibatch's KL), with either loss head: no clip_grad_norm_, no
+    zero_grad and no read-back inside the loop, and one synchronising read of the optimiser's state at the
+    end.  max_grad_norm and target_kl are this call's arguments: the optimiser's own are set to them when
+    they differ.  Since the host no longer learns that the KL crossed the line, it runs every minibatch of
+    every epoch, and a minibatch behind the crossing still pays for its forward and backward pass before
+    its step is skipped on the device: the price of not synchronising.  The dictionary is the same, filled
+    from the device (optimizer_steps = the applied steps, the statistics those of the last applied step,
+    first_approx_kl that of the first), plus gated (skipped minibatches) and grad_norm (the last call's)."""
     torch = store.torch
+    if isinstance(optimizer, DeviceAdam):
+        return _ppo_update_device(agent, optimizer, store, clip_coef, vclip, ent_coef, vf_coef, update_epochs,
+                                  minibatch_size, target_kl, max_grad_norm, generator, entropy_bonus, fused_loss)
     if fused_loss:
         return _ppo_update_fused(agent, optimizer, store, clip_coef, vclip, ent_coef, vf_coef, update_epochs,
                                  minibatch_size, target_kl, max_grad_norm, generator, entropy_bonus)
@@ -388,3 +611,54 @@ def _ppo_update_fused(agent, optimizer, store, clip_coef, vclip, ent_coef, vf_co
         raise ValueError("update_epochs must be at least 1")
     res = {name: float(getattr(last, name)) for name in ("policy_loss", "value_loss", "entropy", "approx_kl")}
     return {**res, "first_approx_kl": float(first_kl), "optimizer_steps": steps, "clipfrac": float(last.clipfrac)}
+
+
+def _ppo_update_device(agent, optimizer, store, clip_coef, vclip, ent_coef, vf_coef, update_epochs, minibatch_size,
+                       target_kl, max_grad_norm, generator, entropy_bonus, fused_loss):
+    """ppo_update with a DeviceAdam: the same minibatches and the same loss (either head), the optimiser's
+    part and the early stop on the device, one read-back at the end."""
+    torch = store.torch
+    if int(update_epochs) < 1:
+        raise ValueError("update_epochs must be at least 1")
+    norm = -1.0 if max_grad_norm is None else float(max_grad_norm)
+    if optimizer.max_grad_norm != norm:
+        optimizer.set_max_grad_norm(norm)
+    if optimizer.target_kl != float(target_kl):
+        optimizer.set_target_kl(target_kl)
+    sign = -1.0 if entropy_bonus else 1.0
+    optimizer.begin_update()
+    for epoch in range(int(update_epochs)):
+        if epoch:
+            optimizer.begin_epoch()
+        for idx in store.minibatches(minibatch_size, generator):
+            if fused_loss:
+                obs = store.gather(idx, normalize=True)["obs"]
+                loss, out = store.loss(idx, agent.actor(obs), agent.critic(obs), clip_coef=clip_coef, vclip=vclip,
+                                       vf_coef=vf_coef, ent_coef=ent_coef, entropy_bonus=entropy_bonus, normalize=True)
+                loss.backward()
+            else:
+                mb = store.gather(idx, normalize=True)
+                _, new_logprob, entropy, new_value = agent.get_action_and_value(mb["obs"], mb["mask"], mb["action"])
+                ratio = (new_logprob - mb["logprob"]).exp()
+                clip_adv = torch.clamp(ratio, 1 - clip_coef, 1 + clip_coef) * mb["adv"]
+                policy_loss = -torch.min(ratio * mb["adv"], clip_adv).mean()
+                v_pred = new_value.squeeze(-1)
+                v_clipped = mb["value"] + torch.clamp(v_pred - mb["value"], -vclip, vclip)
+                value_loss = 0.5 * torch.max((v_pred - mb["ret"]).pow(2), (v_clipped - mb["ret"]).pow(2)).mean()
+                entropy = entropy.mean()
+                loss = policy_loss + vf_coef * value_loss + sign * ent_coef * entropy
+                loss.backward()
+                with torch.no_grad():  # the statistics as one spl_ppo_loss_out_t for the optimiser's latches
+                    approx_kl = (mb["logprob"] - new_logprob).mean()
+                    clipfrac = ((ratio - 1).abs() > clip_coef).float().mean()
+                    buf = torch.zeros(ctypes.sizeof(PpoLossOut) // 8, dtype=torch.float64, device=store.device)
+                    buf[:6] = torch.stack([loss, policy_loss, value_loss, entropy, approx_kl, clipfrac])
+                    out = PPOLossOut(buf, torch)
+            optimizer.step(loss_out=out)
+    st = optimizer.read_state()
+    last = st["last"]
+    res = {name: last[name] for name in ("policy_loss", "value_loss", "entropy", "approx_kl")}
+    res.update(first_approx_kl=st["first"]["approx_kl"], optimizer_steps=st["applied"])
+    if fused_loss:
+        res["clipfrac"] = last["clipfrac"]
+    return {**res, "gated": st["gated"], "grad_norm": st["grad_norm"]}

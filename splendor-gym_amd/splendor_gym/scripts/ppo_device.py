@@ -6,7 +6,8 @@ The loop of the reference's ppo_splendor.py with its argument names where they a
 DualStepVectorEnv against an OpponentPool (current policy with --p-current, else one of --pool-size
 snapshots, drawn per episode), the agent's forward fused (FusedActorCritic), the trajectory in a
 PPORolloutStore, GAE on the device, the update in torch (splendor_gym.ppo; --fused-loss: its loss head
-as one device call).  After each update the
+as one device call; --device-adam: the norm clip, the Adam step and the target-KL stop as one device call
+per minibatch, so that an update reads the device once).  After each update the
 fused agent and the pool re-pack the new weights; every --snapshot-every-updates updates the pool takes
 a snapshot.  --eval-every-updates N evaluates before training and every N updates, --eval-games games
 against each of random, greedy_v1, basic, the agent itself and greedy_v2 in one batch on the device
@@ -45,6 +46,9 @@ def main(argv=None):
                    help="subtract the entropy term (the usual PPO bonus); default: the reference's sign (ppo_update)")
     p.add_argument("--fused-loss", action="store_true",
                    help="the update's loss head as one device call (PPORolloutStore.loss) instead of torch elementwise ops")
+    p.add_argument("--device-adam", action="store_true",
+                   help="the optimiser on the device (splendor_gym.ppo.DeviceAdam) instead of torch.optim.Adam: no per-minibatch "
+                        "read-back; a minibatch behind the target-KL crossing is computed and then skipped")
     p.add_argument("--no-graph", action="store_true", help="run every rollout eagerly instead of replaying a hipGraph")
     p.add_argument("--eval-every-updates", type=int, default=0,
                    help="evaluate before training and every N updates (0: never), as ppo_splendor.py does")
@@ -54,7 +58,7 @@ def main(argv=None):
     import torch
     from ..fused_policy import FusedActorCritic, OpponentPool
     from ..policy import ActorCritic
-    from ..ppo import PPORolloutStore, collect, ppo_update
+    from ..ppo import DeviceAdam, PPORolloutStore, collect, ppo_update
     from ..selfplay import DualStepVectorEnv
 
     dev = torch.device(args.device)
@@ -66,7 +70,10 @@ def main(argv=None):
         agent.load_state_dict(load_file(args.load_path, device=str(dev)))
     elif args.load_path:
         agent.load_state_dict(torch.load(args.load_path, map_location=dev))
-    optimizer = torch.optim.Adam(agent.parameters(), lr=args.lr, eps=1e-5)
+    if args.device_adam:
+        optimizer = DeviceAdam(agent.parameters(), lr=args.lr, eps=1e-5, target_kl=args.target_kl)
+    else:
+        optimizer = torch.optim.Adam(agent.parameters(), lr=args.lr, eps=1e-5)
     agent_k = FusedActorCritic(agent)
     pool = OpponentPool(agent, pool_size=args.pool_size, p_current=args.p_current, seed=args.seed)
     counter = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -96,7 +103,9 @@ def main(argv=None):
         evaluate(0, 0)  # ppo_splendor.py:195-197
     t0 = time.time()
     for update in range(num_updates):
-        if args.lr_anneal:
+        if args.lr_anneal and args.device_adam:
+            optimizer.set_lr(args.lr * (1.0 - update / num_updates))
+        elif args.lr_anneal:
             optimizer.param_groups[0]["lr"] = args.lr * (1.0 - update / num_updates)
         obs, mask = collect(env, agent_k, store, obs, mask, seed=args.seed, graph=not args.no_graph)
         store.compute_gae(gamma=args.gamma, gae_lambda=args.gae_lambda)

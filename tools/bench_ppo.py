@@ -1,8 +1,8 @@
 """Timings of the PPO rollout store (splendor_gym/ppo.py) at the size the engine exists for.
 
-    python tools/bench_ppo.py [--tables 65536] [--steps 128] [--repeats 7] [--loss-json FILE]
+    python tools/bench_ppo.py [--tables 65536] [--steps 128] [--repeats 7] [--loss-json FILE] [--adam-json FILE] [--adam-only]
 
-Prints one JSON line with four comparisons, each arm timed with device events, the arms alternating,
+Prints one JSON line with five comparisons, each arm timed with device events, the arms alternating,
 medians reported:
   1. record: a hipGraph of `steps` config-5 dual steps (tools/bench_selfplay.py's loop: fused fp32 actor,
      opponent pool of 12 trained snapshots) without and with the store's record launches and with the
@@ -13,6 +13,11 @@ medians reported:
   3. gather: spl_ppo_gather at B = 256 and B = 65 536 beside index_select plus the torch expansion.
   4. loss: PPORolloutStore.loss (spl_ppo_loss) beside the torch loss head of ppo_update, forward and backward
      from leaf logits / value tensors, at B = 256 and B = 65 536.
+  5. adam: DeviceAdam.step (spl_ppo_adam) beside clip_grad_norm_ + torch.optim.Adam.step + zero_grad (torch's
+     default and, where the installed torch takes it, fused=True) on the trained agent with one real minibatch's
+     gradients; and one whole ppo_update(fused_loss=True, target_kl=0.02) with either optimiser, timed with
+     the host clock, at the reference's shape (128 steps x 16 tables, minibatch 256, 4 epochs) and at 128 x
+     4 096 with minibatch 65 536.  It builds its own small stores; --adam-only runs nothing else.
 Bytes are the algorithmic bytes each kernel has to move, computed from the shapes below.
 """
 import argparse
@@ -32,6 +37,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--pool-size", type=int, default=12)
     ap.add_argument("--loss-json", default="", help="also write the loss section to this file (profiles/ppo/bench_ppo_loss.json)")
+    ap.add_argument("--adam-json", default="", help="also write the optimiser section to this file (profiles/ppo/bench_ppo_adam.json)")
+    ap.add_argument("--adam-only", action="store_true", help="run the optimiser section alone")
     args = ap.parse_args()
 
     import torch
@@ -70,6 +77,131 @@ def main():
                 b.synchronize()
                 ms[name].append(a.elapsed_time(b) / inner)
         return {name: statistics.median(v) for name, v in ms.items()}
+
+    # ---- 5. the optimiser step (defined here, run last; --adam-only runs nothing else) --------------
+    def adam_section():
+        import copy
+        import time
+        from splendor_gym.ppo import DeviceAdam, collect, ppo_update
+
+        def collected(tables, steps):
+            counter = torch.zeros(1, dtype=torch.int64, device=dev)
+            e = DualStepVectorEnv(tables, device=dev, opponent="random", policy_seed=3, opponent_obs=False,
+                                  step_counter=counter, agent_obs_u8=True)
+            obs, info = e.reset(seed=40)
+            s = PPORolloutStore(steps, tables, dev)
+            collect(e, FusedActorCritic(trained), s, obs, info["action_mask"], seed=5)
+            s.compute_gae()
+            e.close()
+            return s
+
+        trained = net()
+        # (1) the step alone, on the gradients of one real minibatch of 256 positions
+        big = collected(4096, 128)
+        idx = next(iter(big.minibatches(256, torch.Generator(device=dev).manual_seed(0))))
+        obs = big.gather(idx)["obs"]
+        probe = copy.deepcopy(trained)
+        big.loss(idx, probe.actor(obs), probe.critic(obs))[0].backward()
+        grads = [p.grad.clone() for p in probe.parameters()]
+        arms, notes = {}, {}
+
+        def torch_arm(**kw):
+            a = copy.deepcopy(trained)
+            params = list(a.parameters())
+            opt = torch.optim.Adam(params, lr=2.5e-4, eps=1e-5, **kw)
+            own = [g.clone() for g in grads]
+
+            def run():
+                for p, g in zip(params, own):
+                    p.grad = g
+                torch.nn.utils.clip_grad_norm_(params, 0.5)
+                opt.step()
+                opt.zero_grad()
+            return run
+
+        arms["torch"] = torch_arm()
+        try:
+            fused = torch_arm(fused=True)
+            fused()
+            arms["torch_fused"] = fused
+        except Exception as exc:  # the installed torch does not take fused=True on this device
+            notes["torch_fused"] = f"not accepted: {type(exc).__name__}: {exc}"
+        a_dev = copy.deepcopy(trained)
+        p_dev = list(a_dev.parameters())
+        dev_opt = DeviceAdam(p_dev, lr=2.5e-4, eps=1e-5, max_grad_norm=0.5)
+
+        def device_arm():
+            for p, g in zip(p_dev, grads):
+                p.grad = g
+            dev_opt.step()
+
+        arms["device"] = device_arm
+        ms = timed(arms, inner=100)
+        floats = sum(p.numel() for p in p_dev)
+        step = {f"{name}_us": round(v * 1e3, 2) for name, v in ms.items()}
+        step.update(notes)
+        step.update({"floats": floats, "tensors": len(p_dev), "bytes_device": floats * 4 * (1 + 4 + 3),
+                     "ratio_torch_over_device": round(ms["torch"] / ms["device"], 2),
+                     "note": "clip_grad_norm_(0.5) + Adam.step + zero_grad() beside DeviceAdam.step (spl_ppo_adam: two launches), "
+                             "the agent's 12 tensors, gradients of one minibatch of 256; device events around 100 back-to-back "
+                             "calls, arms alternating, medians; bytes_device: the gradients once for the norm, then parameters, "
+                             "gradients and both moments in, parameters and both moments out"})
+        if "torch_fused" in ms:
+            step["ratio_torch_fused_over_device"] = round(ms["torch_fused"] / ms["device"], 2)
+
+        # (2) one whole ppo_update(fused_loss=True), host clock around it and a synchronise, target_kl 0.02
+        def update_arms(store, minibatch):
+            out = {}
+
+            def arm(device_adam):
+                def run():
+                    a = copy.deepcopy(trained)
+                    make = DeviceAdam if device_adam else torch.optim.Adam
+                    opt = make(list(a.parameters()), lr=2.5e-4, eps=1e-5)
+                    gen = torch.Generator(device=dev).manual_seed(0)
+                    torch.cuda.synchronize(dev)
+                    t0 = time.perf_counter()
+                    res = ppo_update(a, opt, store, update_epochs=4, minibatch_size=minibatch, target_kl=0.02, generator=gen,
+                                     fused_loss=True)
+                    torch.cuda.synchronize(dev)
+                    return (time.perf_counter() - t0) * 1e3, res
+                return run
+
+            runs = {"torch_adam": arm(False), "device_adam": arm(True)}
+            for fn in runs.values():
+                fn()
+            times, last = {k: [] for k in runs}, {}
+            for _ in range(args.repeats):
+                for name, fn in runs.items():
+                    t, last[name] = fn()
+                    times[name].append(t)
+            total = store.num_steps * store.num_envs
+            per_epoch = -(-total // minibatch)
+            for name in runs:
+                out[f"{name}_ms"] = round(statistics.median(times[name]), 3)
+                out[f"{name}_optimizer_steps"] = last[name]["optimizer_steps"]
+            out.update({"ratio_torch_over_device": round(out["torch_adam_ms"] / out["device_adam_ms"], 3),
+                        "minibatches_run_torch_adam": "stops each epoch at the crossing",
+                        "minibatches_run_device_adam": 4 * per_epoch, "gated": last["device_adam"]["gated"],
+                        "K": store.num_steps, "T": store.num_envs, "minibatch": minibatch, "epochs": 4})
+            return out
+
+        updates = {"reference_shape": update_arms(collected(16, 128), 256), "large": update_arms(big, 65536)}
+        updates["note"] = ("one ppo_update(fused_loss=True, target_kl=0.02) from the trained checkpoint, host clock from the call to "
+                           "a device synchronise behind it, arms alternating, medians; torch_adam: clip_grad_norm_, "
+                           "torch.optim.Adam and a KL read-back per minibatch (the path before DeviceAdam, unchanged); device_adam: "
+                           "DeviceAdam.step per minibatch, one read-back per update, every minibatch computed")
+        section = {"step": step, "ppo_update": updates}
+        if args.adam_json:
+            with open(args.adam_json, "w") as f:
+                json.dump({"metric": "PPO optimiser step (spl_ppo_adam) and whole updates, one MI355X", "repeats": args.repeats,
+                           "adam": section}, f, indent=1)
+                f.write("\n")
+        return section
+
+    if args.adam_only:
+        print(json.dumps({"metric": "PPO optimiser step, one MI355X", "repeats": args.repeats, "adam": adam_section()}))
+        return
 
     # ---- 1. the dual step without and with recording ---------------------------------------------
     agent = net()
@@ -248,7 +380,7 @@ def main():
                                 "calls of a few microseconds are bound by the host's launch path",
                       "store_bytes": sum(getattr(store, n).numel() * getattr(store, n).element_size() for n in
                                          ("obs_u8", "mask_bits", "action", "logprob", "value", "reward", "done", "adv", "ret")),
-                      "record": rec, "gae": gae, "gather": gather, "loss": loss_head}))
+                      "record": rec, "gae": gae, "gather": gather, "loss": loss_head, "adam": adam_section()}))
     env.close()
 
 
