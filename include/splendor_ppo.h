@@ -19,6 +19,9 @@
  *   spl_ppo_adam     the optimiser step behind the backward pass (ppo_splendor.py:354-361): the
  *                    global-norm clip, torch.optim.Adam's step and the target-KL early stop, decided
  *                    on the device so that the host never waits for a minibatch's KL
+ *   spl_ppo_net_forward / spl_ppo_net_backward   the actor's and the critic's passes around the loss
+ *                    head, reading the observations from the store by position and writing the parameter
+ *                    gradients where spl_ppo_adam reads them
  *
  * The store is step-major [K][T] (K steps, T tables), every plane caller-owned device memory:
  *   obs_u8     uint8  [K][T][300]  the compact rows of spl_step_args_t.obs_u8 (bytes 0..296 the values
@@ -240,6 +243,77 @@ typedef struct {
                                     need to clear it                                                 */
 } spl_ppo_adam_t;
 
+/* ---------------------------------------------------------------------------------------------
+ * spl_ppo_net_forward / spl_ppo_net_backward: the two networks of the update (297 -> 256 -> 256 -> 45 and
+ * 297 -> 256 -> 256 -> 1, tanh; ppo_splendor.py:40-59) around spl_ppo_loss, so that a minibatch is four
+ * calls on one stream: forward -> spl_ppo_loss -> backward -> spl_ppo_adam (SPL_PPO_NET advertises them;
+ * SPL_PPO_ABI is unchanged, nothing above moved).
+ *
+ * Row b stands for the store's flat position idx[b] (duplicates allowed), as in spl_ppo_gather and
+ * spl_ppo_loss.  Its 297 inputs are rebuilt from the obs_u8 plane as spl_ppo_gather does (column 295 =
+ * byte 295 + 256 * byte 297, every other column its byte); no [B][297] float copy exists.  A position
+ * outside [0, K*T) is a bad row: its address is never formed, its logits and value are exact zeros, it
+ * adds nothing to any gradient, and the forward call counts it once in *errors.
+ *
+ * float32 operands, float32 accumulation: every sum is one chain of fused multiply-adds in a fixed order
+ * (the forward sums in input order from the bias; the backward sums over rows in row order), tanh to about
+ * 2 ulp.  No floating-point atomics; the split of the sum over rows is by the constants below, never by the
+ * device, and the partial sums are combined in one fixed order: two calls on the same bytes give the same
+ * bytes.  1 <= B <= SPL_PPO_NET_MAX_ROWS, above it SPL_E_RANGE.  EVERY pointer of both argument blocks
+ * must be 16-byte aligned (SPL_E_ARG otherwise); torch's allocations are.  Argument errors are reported
+ * on the host before anything is launched; nothing is allocated; everything is asynchronous on `stream`. */
+#define SPL_PPO_NET 1
+#define SPL_PPO_NET_MAX_ROWS 65536
+#define SPL_PPO_NET_HIDDEN 256
+#define SPL_PPO_NET_FWD_ROWS 8    /* rows of one forward workgroup (and of one workgroup of the backward's
+                                     first launch)                                                       */
+#define SPL_PPO_NET_BWD_ROWS 128  /* rows of one chunk of the sums over rows                              */
+#define SPL_PPO_NET_BWD_PARTS 32  /* partial sums at the most: chunk c belongs to partial c % 32          */
+
+typedef struct {            /* torch's nn.Linear layout: weight [out][in] row-major, bias [out]; float32 */
+    const float *w1, *b1;   /* [256][297], [256] */
+    const float *w2, *b2;   /* [256][256], [256] */
+    const float *w3, *b3;   /* [n3][256],  [n3]   n3 = 45 (actor) or 1 (critic) */
+} spl_ppo_mlp_t;
+typedef struct { float *w1, *b1, *w2, *b2, *w3, *b3; } spl_ppo_mlp_grad_t;   /* same shapes, out */
+
+/* One launch: a workgroup takes SPL_PPO_NET_FWD_ROWS rows through the three layers of one network. */
+typedef struct {
+    int32_t K, T;
+    int64_t reserved;             /* 0                                                               */
+    const int64_t *idx;           /* [B]                                                             */
+    const uint8_t *obs_u8;        /* the store's plane: [K][T][300]                                  */
+    spl_ppo_mlp_t actor, critic;
+    float *logits;                /* [B][45] out: what spl_ppo_loss_t.logits takes                   */
+    float *new_value;             /* [B] out: what spl_ppo_loss_t.new_value takes                    */
+    void *act;                    /* spl_ppo_net_act_bytes(B) bytes out: both networks' activations
+                                     behind each tanh, in a layout of the implementation's own, for
+                                     the backward call with the same B, idx and weights               */
+    uint64_t *errors;             /* device counter, incremented per bad row (never reset here)      */
+} spl_ppo_net_fwd_t;
+
+/* Three dependent launches.  With dOut = dlogits (actor) or dvalue (critic), H1 / H2 the saved activations
+ * and X the rebuilt inputs, per network, as torch's autograd does for Sequential(Linear, Tanh, Linear,
+ * Tanh, Linear):
+ *   dW3 = dOut^T H2, db3 = SUM_b dOut;  dZ2 = (dOut W3) (1 - H2^2);  dW2 = dZ2^T H1, db2 = SUM_b dZ2;
+ *   dZ1 = (dZ2 W2) (1 - H1^2);  dW1 = dZ1^T X, db1 = SUM_b dZ1.
+ * Launch 1 writes dZ2 and dZ1 to `scratch` (SPL_PPO_NET_FWD_ROWS rows a workgroup).  Launch 2 sums every
+ * 32 x 32 tile of every dW (a bias gradient is one more column, against ones) over the chunks of
+ * SPL_PPO_NET_BWD_ROWS rows of its partial, in row order, into `scratch`.  Launch 3 adds the partials in
+ * order and OVERWRITES the twelve gradients: nothing is accumulated into, there is no zero_grad. */
+typedef struct {
+    int32_t K, T;
+    int64_t reserved;             /* 0                                                               */
+    const int64_t *idx;           /* [B]: the forward call's                                         */
+    const uint8_t *obs_u8;        /* [K][T][300]                                                     */
+    spl_ppo_mlp_t actor, critic;  /* the forward call's (b1, b2, b3 are not read)                    */
+    const float *dlogits;         /* [B][45] as spl_ppo_loss writes them                             */
+    const float *dvalue;          /* [B]                                                             */
+    const void *act;              /* the forward call's                                              */
+    spl_ppo_mlp_grad_t actor_grad, critic_grad; /* out                                               */
+    void *scratch;                /* spl_ppo_net_scratch_bytes(B) bytes; no need to clear it          */
+} spl_ppo_net_bwd_t;
+
 /* n rows of one step into the store */
 int spl_ppo_record(int32_t n, const spl_ppo_record_t *args, void *stream);
 /* bytes of spl_ppo_gae_t.scratch for T tables (SPL_E_ARG for T < 1) */
@@ -263,6 +337,14 @@ int spl_ppo_adam_begin(spl_ppo_adam_state_t *state, int32_t what, void *stream);
 /* norm clip, Adam step and KL gate of one minibatch: two launches, asynchronous on `stream`, nothing
  * allocated */
 int spl_ppo_adam(const spl_ppo_adam_t *args, void *stream);
+/* bytes of spl_ppo_net_fwd_t.act / spl_ppo_net_bwd_t.scratch for B rows (SPL_E_ARG for B < 1, SPL_E_RANGE
+ * above SPL_PPO_NET_MAX_ROWS) */
+int64_t spl_ppo_net_act_bytes(int32_t B);
+int64_t spl_ppo_net_scratch_bytes(int32_t B);
+/* both networks' outputs for B positions: one launch */
+int spl_ppo_net_forward(int32_t B, const spl_ppo_net_fwd_t *args, void *stream);
+/* both networks' twelve parameter gradients, overwritten: three launches */
+int spl_ppo_net_backward(int32_t B, const spl_ppo_net_bwd_t *args, void *stream);
 
 #ifdef __cplusplus
 }

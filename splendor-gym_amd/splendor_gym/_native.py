@@ -138,7 +138,30 @@ class PpoAdam(ctypes.Structure):
                [(k, c_void_p) for k in ("exp_avg", "exp_avg_sq", "state", "approx_kl", "loss_out", "scratch")]
 
 
-EVAL_ABI = 1                       # SPL_EVAL_ABI (include/splendor_eval.h)
+PPO_NET_MAX_ROWS, PPO_NET_HIDDEN = 65536, 256                     # SPL_PPO_NET_*
+PPO_NET_FWD_ROWS, PPO_NET_BWD_ROWS, PPO_NET_BWD_PARTS = 8, 128, 32  # rows per forward tile, per backward partial's chunk
+
+
+class PpoMlp(ctypes.Structure):
+    """spl_ppo_mlp_t and spl_ppo_mlp_grad_t (include/splendor_ppo.h)"""
+    _fields_ = [(k, c_void_p) for k in ("w1", "b1", "w2", "b2", "w3", "b3")]
+
+
+class PpoNetFwd(ctypes.Structure):
+    """spl_ppo_net_fwd_t (include/splendor_ppo.h)"""
+    _fields_ = [("K", c_int32), ("T", c_int32), ("reserved", c_int64), ("idx", c_void_p), ("obs_u8", c_void_p),
+                ("actor", PpoMlp), ("critic", PpoMlp), ("logits", c_void_p), ("new_value", c_void_p), ("act", c_void_p),
+                ("errors", c_void_p)]
+
+
+class PpoNetBwd(ctypes.Structure):
+    """spl_ppo_net_bwd_t (include/splendor_ppo.h)"""
+    _fields_ = [("K", c_int32), ("T", c_int32), ("reserved", c_int64), ("idx", c_void_p), ("obs_u8", c_void_p),
+                ("actor", PpoMlp), ("critic", PpoMlp), ("dlogits", c_void_p), ("dvalue", c_void_p), ("act", c_void_p),
+                ("actor_grad", PpoMlp), ("critic_grad", PpoMlp), ("scratch", c_void_p)]
+
+
+EVAL_ABI = 1                     # SPL_EVAL_ABI (include/splendor_eval.h)
 POLICY_GREEDY_V2, EVAL_KEEP = 3, -1  # SPL_POLICY_GREEDY_V2, SPL_EVAL_KEEP: spl_eval_scripted_act only
 EVAL_COLS = 8                      # wins, losses, draws, unfinished, sum turns, sum prestige, checks, illegal
 
@@ -241,6 +264,10 @@ SIGNATURES = {
     "spl_ppo_adam_scratch_bytes": ([c_int64], c_int64),
     "spl_ppo_adam_begin": ([c_void_p, c_int32, c_void_p], c_int32),
     "spl_ppo_adam": ([ctypes.POINTER(PpoAdam), c_void_p], c_int32),
+    "spl_ppo_net_act_bytes": ([c_int32], c_int64),
+    "spl_ppo_net_scratch_bytes": ([c_int32], c_int64),
+    "spl_ppo_net_forward": ([c_int32, ctypes.POINTER(PpoNetFwd), c_void_p], c_int32),
+    "spl_ppo_net_backward": ([c_int32, ctypes.POINTER(PpoNetBwd), c_void_p], c_int32),
     # include/splendor_eval.h
     "spl_eval_abi_version": ([], c_int32),
     "spl_eval_scripted_act": ([c_int32, ctypes.POINTER(EvalAct), c_void_p], c_int32),

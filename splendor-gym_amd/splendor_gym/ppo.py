@@ -19,7 +19,12 @@ masks: 2.8 GB instead of 10.4 GB at 128 steps x 65 536 tables):
     global-norm clip, torch.optim.Adam's step and the target-KL early stop, decided on the device, so that
     ``ppo_update`` with it reads the device once per update instead of once per minibatch.
 
-The two networks' forward and backward passes stay in torch.  There is no CPU fallback.
+  * ``DeviceNets``  the two networks' forward and backward passes as device calls (spl_ppo_net_forward /
+    spl_ppo_net_backward) that read the observations from the store by position and write the parameter
+    gradients where the optimiser reads them; ``ppo_update(device_nets=True)`` runs a minibatch as
+    forward -> loss -> backward -> step without autograd.
+
+Without ``device_nets`` the two networks' passes stay in torch.  There is no CPU fallback.
 """
 import ctypes
 
@@ -520,9 +525,124 @@ class DeviceAdam:
         self.set_eps(group["eps"])
 
 
+class DeviceNets:
+    """The actor's and the critic's forward and backward passes of the update as device calls
+    (spl_ppo_net_forward / spl_ppo_net_backward, include/splendor_ppo.h): no autograd graph, no gathered
+    float observations, no zero_grad.  `agent` is an ActorCritic whose twelve parameters are float32,
+    contiguous, of the reference's shapes (297 -> 256 -> 256 -> 45 | 1) and on one GPU; anything else is a
+    ValueError (there is no CPU fallback).  The parameters stay where torch put them and are read in place, so
+    optimiser steps and load_state_dict are seen by the next call.
+
+    A parameter without a .grad gets one here, once; backward() OVERWRITES every p.grad (and puts its own
+    tensor back where an optimiser has set p.grad to None), so a DeviceAdam or a torch.optim optimiser over
+    the same parameters reads the gradients in place.  The outputs, the saved activations and the scratch
+    are kept per B, sized on first use: what forward() returned belongs to the latest call with that B."""
+    MAX_ROWS = _native.PPO_NET_MAX_ROWS
+
+    def __init__(self, agent):
+        import torch
+        nets = []
+        for name, n3 in (("actor", NUM_ACTIONS), ("critic", 1)):
+            net = getattr(agent, name, None)
+            if not isinstance(net, torch.nn.Sequential) or len(net) != 5 or \
+                    not all(isinstance(net[i], torch.nn.Linear) and net[i].bias is not None for i in (0, 2, 4)):
+                raise ValueError(f"agent.{name} must be Sequential(Linear, Tanh, Linear, Tanh, Linear) with biases")
+            ps = [net[0].weight, net[0].bias, net[2].weight, net[2].bias, net[4].weight, net[4].bias]
+            H = _native.PPO_NET_HIDDEN
+            shapes = ((H, OBS_DIM), (H,), (H, H), (H,), (n3, H), (n3,))
+            for p, shape, field in zip(ps, shapes, ("w1", "b1", "w2", "b2", "w3", "b3")):
+                if p.dtype != torch.float32 or not p.is_contiguous() or tuple(p.shape) != shape:
+                    raise ValueError(f"{name}.{field} must be a contiguous float32 {list(shape)} tensor, not "
+                                     f"{p.dtype} {list(p.shape)}{'' if p.is_contiguous() else ' (not contiguous)'}")
+            nets.append(ps)
+        self.torch, self.lib = _native.require_gpu(), _native.load_library()
+        self.params = nets[0] + nets[1]  # the actor's six, then the critic's
+        self.device = self.params[0].device
+        if self.device.type != "cuda" or any(p.device != self.device for p in self.params):
+            raise ValueError("DeviceNets needs every parameter on one GPU (no CPU fallback)")
+        for p in self.params:
+            if p.grad is None:
+                p.grad = torch.zeros_like(p)
+        self._grads = [p.grad for p in self.params]
+        self._bufs = {}
+
+    def _stream(self):
+        return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _mlp(self, tensors):
+        return _native.PpoMlp(*(x.data_ptr() for x in tensors))
+
+    def _buffers(self, B):
+        bufs = self._bufs.get(B)
+        if bufs is None:
+            t = self.torch
+            e = lambda n: t.empty(n, dtype=t.float32, device=self.device)
+            bufs = {"logits": e((B, NUM_ACTIONS)), "value": e((B,)),
+                    "act": e(int(check(self.lib, self.lib.spl_ppo_net_act_bytes(B))) // 4),
+                    "scratch": e(int(check(self.lib, self.lib.spl_ppo_net_scratch_bytes(B))) // 4)}
+            self._bufs[B] = bufs
+        return bufs
+
+    def _idx(self, store, idx):
+        t = self.torch
+        if store.device != self.device:
+            raise ValueError(f"the store must be on {self.device}")
+        if not isinstance(idx, t.Tensor) or idx.dtype != t.int64 or idx.dim() != 1 or not idx.is_contiguous() or \
+                idx.device != self.device or idx.numel() < 1:
+            raise ValueError(f"idx must be a non-empty contiguous int64 [B] tensor on {self.device}")
+        if idx.numel() > self.MAX_ROWS:
+            raise ValueError(f"DeviceNets takes at most {self.MAX_ROWS} rows a call (SPL_PPO_NET_MAX_ROWS), not {idx.numel()}")
+        return idx if idx.data_ptr() % 16 == 0 else idx.clone()  # a slice of a permutation may start anywhere
+
+    def forward(self, store, idx):
+        """(logits float32 [B, 45], value float32 [B]) of the store's flat positions idx (int64 [B], as for
+        store.gather), plain tensors this object owns.  A position outside the store gives zeros and
+        counts in store.errors.  Asynchronous."""
+        idx = self._idx(store, idx)
+        B = idx.numel()
+        bufs = self._buffers(B)
+        a = _native.PpoNetFwd(K=store.num_steps, T=store.num_envs, reserved=0, idx=idx.data_ptr(),
+                              obs_u8=store.obs_u8.data_ptr(), actor=self._mlp(self.params[:6]),
+                              critic=self._mlp(self.params[6:]), logits=bufs["logits"].data_ptr(),
+                              new_value=bufs["value"].data_ptr(), act=bufs["act"].data_ptr(), errors=store.errors.data_ptr())
+        with self.torch.cuda.device(self.device):
+            check(self.lib, self.lib.spl_ppo_net_forward(B, ctypes.byref(a), self._stream()))
+        bufs["idx"] = idx
+        return bufs["logits"], bufs["value"]
+
+    def backward(self, store, idx, dlogits, dvalue):
+        """Every p.grad = the gradient that dlogits (float32 [B, 45]) and dvalue (float32 [B] or [B, 1]) give
+        through the two networks, for the latest forward() with this B (same store, same idx, parameters
+        untouched since).  Overwrites, never accumulates.  Asynchronous."""
+        t = self.torch
+        idx = self._idx(store, idx)
+        B = idx.numel()
+        if B not in self._bufs:
+            raise ValueError(f"backward() needs a forward() with the same B = {B} before it")
+        bufs = self._bufs[B]
+        for x, shapes, what in ((dlogits, ((B, NUM_ACTIONS),), "dlogits"), (dvalue, ((B,), (B, 1)), "dvalue")):
+            if not isinstance(x, t.Tensor) or x.dtype != t.float32 or tuple(x.shape) not in shapes or not x.is_contiguous() or \
+                    x.device != self.device:
+                raise ValueError(f"{what} must be a contiguous float32 {list(shapes[0])} tensor on {self.device}")
+        for p, g in zip(self.params, self._grads):
+            if p.grad is None:
+                p.grad = g
+            elif p.grad.dtype != t.float32 or not p.grad.is_contiguous() or p.grad.shape != p.shape or p.grad.device != self.device:
+                raise ValueError("every p.grad must be a contiguous float32 tensor of its parameter's shape on the device")
+        grads = [p.grad for p in self.params]
+        a = _native.PpoNetBwd(K=store.num_steps, T=store.num_envs, reserved=0, idx=idx.data_ptr(),
+                              obs_u8=store.obs_u8.data_ptr(), actor=self._mlp(self.params[:6]),
+                              critic=self._mlp(self.params[6:]), dlogits=dlogits.data_ptr(), dvalue=dvalue.data_ptr(),
+                              act=bufs["act"].data_ptr(), actor_grad=self._mlp(grads[:6]), critic_grad=self._mlp(grads[6:]),
+                              scratch=bufs["scratch"].data_ptr())
+        with t.cuda.device(self.device):
+            check(self.lib, self.lib.spl_ppo_net_backward(B, ctypes.byref(a), self._stream()))
+        bufs["idx"] = idx
+
+
 def ppo_update(agent, optimizer, store, clip_coef=0.2, vclip=0.2, ent_coef=0.03, vf_coef=0.5, update_epochs=4,
                minibatch_size=256, target_kl=0.02, max_grad_norm=0.5, generator=None, entropy_bonus=False,
-               fused_loss=False):
+               fused_loss=False, device_nets=False):
     """The update of ppo_splendor.py:327-361 over store.minibatches (call store.compute_gae first):
     clipped policy loss, clipped value loss, the entropy term, grad-norm clip at 0.5 and the target-KL
     early stop, which like the reference's `break` ends the current epoch only.
@@ -547,8 +667,19 @@ def ppo_update(agent, optimizer, store, clip_coef=0.2, vclip=0.2, ent_coef=0.03,
     every epoch, and a minibatch behind the crossing still pays for its forward and backward pass before
     its step is skipped on the device: the price of not synchronising.  The dictionary is the same, filled
     from the device (optimizer_steps = the applied steps, the statistics those of the last applied step,
-    first_approx_kl that of the first), plus gated (skipped minibatches) and grad_norm (the last call's)."""
+    first_approx_kl that of the first), plus gated (skipped minibatches) and grad_norm (the last call's).
+
+    device_nets=True (or a DeviceNets over this agent, which keeps its buffers from update to update) also
+    moves the two networks' passes to the device and implies the fused loss head: a minibatch is
+    DeviceNets.forward -> the loss launch -> DeviceNets.backward -> optimizer.step, with no autograd, no gather
+    and no zero_grad.  With a DeviceAdam that is four device calls and one read-back per update; with a
+    torch.optim optimiser clip_grad_norm_, step() and the per-minibatch KL read-back stay.  The dictionary is
+    that of the same optimiser's fused-loss path."""
     torch = store.torch
+    if device_nets is not False and device_nets is not None:
+        nets = device_nets if isinstance(device_nets, DeviceNets) else DeviceNets(agent)
+        return _ppo_update_nets(agent, nets, optimizer, store, clip_coef, vclip, ent_coef, vf_coef, update_epochs,
+                                minibatch_size, target_kl, max_grad_norm, generator, entropy_bonus)
     if isinstance(optimizer, DeviceAdam):
         return _ppo_update_device(agent, optimizer, store, clip_coef, vclip, ent_coef, vf_coef, update_epochs,
                                   minibatch_size, target_kl, max_grad_norm, generator, entropy_bonus, fused_loss)
@@ -609,6 +740,53 @@ def _ppo_update_fused(agent, optimizer, store, clip_coef, vclip, ent_coef, vf_co
                 break
     if last is None:
         raise ValueError("update_epochs must be at least 1")
+    res = {name: float(getattr(last, name)) for name in ("policy_loss", "value_loss", "entropy", "approx_kl")}
+    return {**res, "first_approx_kl": float(first_kl), "optimizer_steps": steps, "clipfrac": float(last.clipfrac)}
+
+
+def _ppo_update_nets(agent, nets, optimizer, store, clip_coef, vclip, ent_coef, vf_coef, update_epochs, minibatch_size,
+                     target_kl, max_grad_norm, generator, entropy_bonus):
+    """ppo_update(device_nets=...): the same minibatches; forward, loss head and backward as device calls."""
+    torch = store.torch
+    if int(update_epochs) < 1:
+        raise ValueError("update_epochs must be at least 1")
+    if nets.params[0] is not agent.actor[0].weight or nets.params[6] is not agent.critic[0].weight:
+        raise ValueError("device_nets was built over another agent's parameters")
+    on_device = isinstance(optimizer, DeviceAdam)
+    if on_device:
+        norm = -1.0 if max_grad_norm is None else float(max_grad_norm)
+        if optimizer.max_grad_norm != norm:
+            optimizer.set_max_grad_norm(norm)
+        if optimizer.target_kl != float(target_kl):
+            optimizer.set_target_kl(target_kl)
+        optimizer.begin_update()
+    coef = (float(clip_coef), float(vclip), float(vf_coef), -float(ent_coef) if entropy_bonus else float(ent_coef))
+    last, first_kl, steps = None, None, 0
+    for epoch in range(int(update_epochs)):
+        if on_device and epoch:
+            optimizer.begin_epoch()
+        for idx in store.minibatches(minibatch_size, generator):
+            logits, value = nets.forward(store, idx)
+            bufs = store._launch_loss(idx, logits, value, coef, True)
+            nets.backward(store, idx, bufs["dlogits"], bufs["dvalue"])
+            out = bufs["out"]
+            if on_device:
+                optimizer.step(loss_out=out)
+                continue
+            torch.nn.utils.clip_grad_norm_(agent.parameters(), max_grad_norm)
+            optimizer.step()
+            steps += 1
+            if first_kl is None:
+                first_kl = out.approx_kl.clone()
+            last = out
+            if target_kl > 0 and out.approx_kl.item() > target_kl:
+                break
+    if on_device:
+        st = optimizer.read_state()
+        last = st["last"]
+        res = {name: last[name] for name in ("policy_loss", "value_loss", "entropy", "approx_kl")}
+        res.update(first_approx_kl=st["first"]["approx_kl"], optimizer_steps=st["applied"], clipfrac=last["clipfrac"])
+        return {**res, "gated": st["gated"], "grad_norm": st["grad_norm"]}
     res = {name: float(getattr(last, name)) for name in ("policy_loss", "value_loss", "entropy", "approx_kl")}
     return {**res, "first_approx_kl": float(first_kl), "optimizer_steps": steps, "clipfrac": float(last.clipfrac)}
 

@@ -7,7 +7,8 @@ DualStepVectorEnv against an OpponentPool (current policy with --p-current, else
 snapshots, drawn per episode), the agent's forward fused (FusedActorCritic), the trajectory in a
 PPORolloutStore, GAE on the device, the update in torch (splendor_gym.ppo; --fused-loss: its loss head
 as one device call; --device-adam: the norm clip, the Adam step and the target-KL stop as one device call
-per minibatch, so that an update reads the device once).  After each update the
+per minibatch, so that an update reads the device once; --device-nets: the two networks' forward and
+backward passes as device calls too, a minibatch then being four device calls).  After each update the
 fused agent and the pool re-pack the new weights; every --snapshot-every-updates updates the pool takes
 a snapshot.  --eval-every-updates N evaluates before training and every N updates, --eval-games games
 against each of random, greedy_v1, basic, the agent itself and greedy_v2 in one batch on the device
@@ -49,6 +50,9 @@ def main(argv=None):
     p.add_argument("--device-adam", action="store_true",
                    help="the optimiser on the device (splendor_gym.ppo.DeviceAdam) instead of torch.optim.Adam: no per-minibatch "
                         "read-back; a minibatch behind the target-KL crossing is computed and then skipped")
+    p.add_argument("--device-nets", action="store_true",
+                   help="the two networks' forward and backward passes of the update as device calls "
+                        "(splendor_gym.ppo.DeviceNets) instead of torch autograd; implies --fused-loss")
     p.add_argument("--no-graph", action="store_true", help="run every rollout eagerly instead of replaying a hipGraph")
     p.add_argument("--eval-every-updates", type=int, default=0,
                    help="evaluate before training and every N updates (0: never), as ppo_splendor.py does")
@@ -58,7 +62,7 @@ def main(argv=None):
     import torch
     from ..fused_policy import FusedActorCritic, OpponentPool
     from ..policy import ActorCritic
-    from ..ppo import DeviceAdam, PPORolloutStore, collect, ppo_update
+    from ..ppo import DeviceAdam, DeviceNets, PPORolloutStore, collect, ppo_update
     from ..selfplay import DualStepVectorEnv
 
     dev = torch.device(args.device)
@@ -74,8 +78,9 @@ def main(argv=None):
         optimizer = DeviceAdam(agent.parameters(), lr=args.lr, eps=1e-5, target_kl=args.target_kl)
     else:
         optimizer = torch.optim.Adam(agent.parameters(), lr=args.lr, eps=1e-5)
+    nets = DeviceNets(agent) if args.device_nets else False
     agent_k = FusedActorCritic(agent)
-    pool = OpponentPool(agent, pool_size=args.pool_size, p_current=args.p_current, seed=args.seed)
+    pool =OpponentPool(agent, pool_size=args.pool_size, p_current=args.p_current, seed=args.seed)
     counter = torch.zeros(1, dtype=torch.int64, device=dev)
     env = DualStepVectorEnv(args.num_envs, device=dev, opponent=pool, opponent_obs=False, step_counter=counter,
                             agent_obs_u8=True)
@@ -114,7 +119,7 @@ def main(argv=None):
                          ent_coef=args.ent_coef + (args.ent_coef_final - args.ent_coef) * progress,
                          vf_coef=args.vf_coef, update_epochs=args.update_epochs, minibatch_size=args.minibatch_size,
                          target_kl=args.target_kl, generator=gen, entropy_bonus=args.entropy_bonus,
-                         fused_loss=args.fused_loss)
+                         fused_loss=args.fused_loss or args.device_nets, device_nets=nets)
         agent_k.refresh()
         pool.refresh()
         if (update + 1) % max(1, args.snapshot_every_updates) == 0:
