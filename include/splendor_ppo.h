@@ -346,6 +346,24 @@ int spl_ppo_net_forward(int32_t B, const spl_ppo_net_fwd_t *args, void *stream);
 /* both networks' twelve parameter gradients, overwritten: three launches */
 int spl_ppo_net_backward(int32_t B, const spl_ppo_net_bwd_t *args, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * spl_ppo_net_forward_tiled / spl_ppo_net_backward_tiled: the same two passes for large minibatches
+ * (SPL_PPO_NET_TILED advertises them; SPL_PPO_ABI is unchanged, nothing above moved).  Rows are blocked as
+ * well as units: a workgroup takes SPL_PPO_NET_TILE_ROWS rows through one layer as an LDS-tiled product on
+ * the f32-input matrix instruction, so a weight element fetched once serves that many rows.
+ *
+ * Same argument blocks, same buffers of the same sizes, same refusals, same treatment of bad rows, and THE
+ * SAME BYTES in every output: the matrix instruction is a k-ordered chain of fused multiply-adds from its
+ * accumulator's start value, which is what the calls above compute, and the sums over rows keep the split
+ * by SPL_PPO_NET_BWD_ROWS and SPL_PPO_NET_BWD_PARTS.  `act` is [network][layer][B][256] and the head of
+ * `scratch` [network][dZ2, dZ1][B][256] for both pairs, so either forward goes with either backward, and a
+ * caller may choose by B without the training run changing.  Forward: three launches (layer 1, layer 2,
+ * the output layers); backward: four (dZ2, dZ1, the sums over rows, the ordered combination). */
+#define SPL_PPO_NET_TILED 1
+#define SPL_PPO_NET_TILE_ROWS 64  /* rows of one workgroup of the tiled forward and dZ launches          */
+int spl_ppo_net_forward_tiled(int32_t B, const spl_ppo_net_fwd_t *args, void *stream);
+int spl_ppo_net_backward_tiled(int32_t B, const spl_ppo_net_bwd_t *args, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -140,6 +140,7 @@ class PpoAdam(ctypes.Structure):
 
 PPO_NET_MAX_ROWS, PPO_NET_HIDDEN = 65536, 256                     # SPL_PPO_NET_*
 PPO_NET_FWD_ROWS, PPO_NET_BWD_ROWS, PPO_NET_BWD_PARTS = 8, 128, 32  # rows per forward tile, per backward partial's chunk
+PPO_NET_TILED, PPO_NET_TILE_ROWS = 1, 64  # SPL_PPO_NET_TILED; rows per workgroup of the tiled forward and dZ launches
 
 
 class PpoMlp(ctypes.Structure):
@@ -268,6 +269,8 @@ SIGNATURES = {
     "spl_ppo_net_scratch_bytes": ([c_int32], c_int64),
     "spl_ppo_net_forward": ([c_int32, ctypes.POINTER(PpoNetFwd), c_void_p], c_int32),
     "spl_ppo_net_backward": ([c_int32, ctypes.POINTER(PpoNetBwd), c_void_p], c_int32),
+    "spl_ppo_net_forward_tiled": ([c_int32, ctypes.POINTER(PpoNetFwd), c_void_p], c_int32),
+    "spl_ppo_net_backward_tiled": ([c_int32, ctypes.POINTER(PpoNetBwd), c_void_p], c_int32),
     # include/splendor_eval.h
     "spl_eval_abi_version": ([], c_int32),
     "spl_eval_scripted_act": ([c_int32, ctypes.POINTER(EvalAct), c_void_p], c_int32),
@@ -275,6 +278,10 @@ SIGNATURES = {
     "spl_eval_tally": ([c_int32, ctypes.POINTER(EvalTally), c_void_p], c_int32),
     "spl_eval_reduce": ([c_int32, c_int32, ctypes.POINTER(EvalReduce), c_void_p], c_int32),
 }
+
+# what a library built from an earlier header may lack (SPLENDOR_AMD_LIB can name one): it still loads, and
+# what needs these asks has_net_tiled() first
+OPTIONAL = ("spl_ppo_net_forward_tiled", "spl_ppo_net_backward_tiled")
 
 
 class NativeError(RuntimeError):
@@ -303,6 +310,8 @@ def load_library():
                           "`python -c 'import __graft_entry__ as g; g.build()'` (no CPU fallback exists)")
     lib = ctypes.CDLL(path)
     for name, (argtypes, restype) in SIGNATURES.items():
+        if name in OPTIONAL and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = restype
@@ -310,6 +319,11 @@ def load_library():
         raise ImportError(f"splendor_gym: ABI version {lib.spl_abi_version()} != {ABI_VERSION}")
     _LIB = lib
     return lib
+
+
+def has_net_tiled(lib):
+    """the library exports spl_ppo_net_forward_tiled / spl_ppo_net_backward_tiled (SPL_PPO_NET_TILED)"""
+    return all(hasattr(lib, name) for name in OPTIONAL)
 
 
 def check(lib, code):

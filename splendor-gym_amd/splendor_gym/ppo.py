@@ -22,7 +22,9 @@ masks: 2.8 GB instead of 10.4 GB at 128 steps x 65 536 tables):
   * ``DeviceNets``  the two networks' forward and backward passes as device calls (spl_ppo_net_forward /
     spl_ppo_net_backward) that read the observations from the store by position and write the parameter
     gradients where the optimiser reads them; ``ppo_update(device_nets=True)`` runs a minibatch as
-    forward -> loss -> backward -> step without autograd.
+    forward -> loss -> backward -> step without autograd.  ``DeviceNets(agent, tiled=True | "auto")`` runs
+    the passes on the LDS-tiled matrix-core kernels built for minibatches of thousands of rows
+    (spl_ppo_net_forward_tiled / spl_ppo_net_backward_tiled), with the same bytes.
 
 Without ``device_nets`` the two networks' passes stay in torch.  There is no CPU fallback.
 """
@@ -536,11 +538,21 @@ class DeviceNets:
     A parameter without a .grad gets one here, once; backward() OVERWRITES every p.grad (and puts its own
     tensor back where an optimiser has set p.grad to None), so a DeviceAdam or a torch.optim optimiser over
     the same parameters reads the gradients in place.  The outputs, the saved activations and the scratch
-    are kept per B, sized on first use: what forward() returned belongs to the latest call with that B."""
-    MAX_ROWS = _native.PPO_NET_MAX_ROWS
+    are kept per B, sized on first use: what forward() returned belongs to the latest call with that B.
 
-    def __init__(self, agent):
+    `tiled` chooses between the two pairs of calls, which give the same bytes in the same buffers: False
+    (the default) the 8-rows-a-workgroup passes built for minibatches of a few hundred rows, True the
+    LDS-tiled matrix-core passes (spl_ppo_net_forward_tiled / spl_ppo_net_backward_tiled) built for tens of
+    thousands, "auto" the tiled ones from TILED_MIN_ROWS rows upward.  A library without the tiled calls is
+    a RuntimeError for anything but False."""
+    MAX_ROWS = _native.PPO_NET_MAX_ROWS
+    TILE_ROWS = _native.PPO_NET_TILE_ROWS
+    TILED_MIN_ROWS = 4096  # the smallest benchmarked B at which the tiled passes beat the others (profiles/ppo/bench_ppo_nets_tiled.json)
+
+    def __init__(self, agent, tiled=False):
         import torch
+        if not any(tiled is v for v in (False, True)) and tiled != "auto":
+            raise ValueError(f"tiled must be False, True or 'auto', not {tiled!r}")
         nets = []
         for name, n3 in (("actor", NUM_ACTIONS), ("critic", 1)):
             net = getattr(agent, name, None)
@@ -565,6 +577,13 @@ class DeviceNets:
                 p.grad = torch.zeros_like(p)
         self._grads = [p.grad for p in self.params]
         self._bufs = {}
+        self.tiled = tiled
+        if tiled is not False and not _native.has_net_tiled(self.lib):
+            raise RuntimeError(f"DeviceNets(tiled={tiled!r}) needs spl_ppo_net_forward_tiled / spl_ppo_net_backward_tiled "
+                               f"(SPL_PPO_NET_TILED), which {_native.lib_path()} does not export; rebuild the library")
+
+    def _use_tiled(self, B):
+        return self.tiled is True or (self.tiled == "auto" and B >= self.TILED_MIN_ROWS)
 
     def _stream(self):
         return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
@@ -606,7 +625,8 @@ class DeviceNets:
                               critic=self._mlp(self.params[6:]), logits=bufs["logits"].data_ptr(),
                               new_value=bufs["value"].data_ptr(), act=bufs["act"].data_ptr(), errors=store.errors.data_ptr())
         with self.torch.cuda.device(self.device):
-            check(self.lib, self.lib.spl_ppo_net_forward(B, ctypes.byref(a), self._stream()))
+            call = self.lib.spl_ppo_net_forward_tiled if self._use_tiled(B) else self.lib.spl_ppo_net_forward
+            check(self.lib, call(B, ctypes.byref(a), self._stream()))
         bufs["idx"] = idx
         return bufs["logits"], bufs["value"]
 
@@ -636,7 +656,8 @@ class DeviceNets:
                               act=bufs["act"].data_ptr(), actor_grad=self._mlp(grads[:6]), critic_grad=self._mlp(grads[6:]),
                               scratch=bufs["scratch"].data_ptr())
         with t.cuda.device(self.device):
-            check(self.lib, self.lib.spl_ppo_net_backward(B, ctypes.byref(a), self._stream()))
+            call = self.lib.spl_ppo_net_backward_tiled if self._use_tiled(B) else self.lib.spl_ppo_net_backward
+            check(self.lib, call(B, ctypes.byref(a), self._stream()))
         bufs["idx"] = idx
 
 

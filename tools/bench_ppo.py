@@ -20,9 +20,10 @@ medians reported:
      the host clock, at the reference's shape (128 steps x 16 tables, minibatch 256, 4 epochs) and at 128 x
      4 096 with minibatch 65 536.  It builds its own small stores; --adam-only runs nothing else.
   6. nets (--nets-only, not part of the default run): DeviceNets.forward + backward (spl_ppo_net_forward /
-     spl_ppo_net_backward) beside store.gather + the two torch networks + torch.autograd.backward for fixed
-     dlogits / dvalue, at B = 256 and B = 65 536; and one whole ppo_update(fused_loss=True, target_kl=0.02)
-     with DeviceAdam without and with device_nets, at the same two shapes as in 5.
+     spl_ppo_net_backward) and DeviceNets(tiled=True) (spl_ppo_net_forward_tiled / spl_ppo_net_backward_tiled)
+     beside store.gather + the two torch networks + torch.autograd.backward for fixed dlogits / dvalue, at
+     B = 256, 4 096, 16 384 and 65 536; and one whole ppo_update(fused_loss=True, target_kl=0.02) with
+     DeviceAdam without device_nets, with them and with the tiled ones, at the same two shapes as in 5.
 Bytes are the algorithmic bytes each kernel has to move, computed from the shapes below.
 """
 import argparse
@@ -44,7 +45,7 @@ def main():
     ap.add_argument("--loss-json", default="", help="also write the loss section to this file (profiles/ppo/bench_ppo_loss.json)")
     ap.add_argument("--adam-json", default="", help="also write the optimiser section to this file (profiles/ppo/bench_ppo_adam.json)")
     ap.add_argument("--adam-only", action="store_true", help="run the optimiser section alone")
-    ap.add_argument("--nets-json", default="", help="also write the network section to this file (profiles/ppo/bench_ppo_nets.json)")
+    ap.add_argument("--nets-json", default="", help="also write the network section to this file (profiles/ppo/bench_ppo_nets_tiled.json)")
     ap.add_argument("--nets-only", action="store_true", help="run the network-pass section alone")
     args = ap.parse_args()
 
@@ -228,17 +229,21 @@ def main():
         big = collected(4096, 128)
         gen = torch.Generator(device=dev).manual_seed(0)
         passes = {}
-        for B in (256, 65536):
+        for B in (256, 4096, 16384, 65536):
             idx = torch.randperm(big.num_steps * big.num_envs, device=dev, generator=gen)[:B].contiguous()
             dlogits = torch.randn(B, 45, device=dev, generator=gen) / B
             dvalue = torch.randn(B, device=dev, generator=gen) / B
-            a_dev, a_ref = copy.deepcopy(trained), copy.deepcopy(trained)
-            nets = DeviceNets(a_dev)
+            a_dev, a_ref, a_tiled = copy.deepcopy(trained), copy.deepcopy(trained), copy.deepcopy(trained)
+            nets, tiled = DeviceNets(a_dev), DeviceNets(a_tiled, tiled=True)
             ref_params = list(a_ref.parameters())
 
             def device_arm():
                 nets.forward(big, idx)
                 nets.backward(big, idx, dlogits, dvalue)
+
+            def tiled_arm():
+                tiled.forward(big, idx)
+                tiled.backward(big, idx, dlogits, dvalue)
 
             def torch_arm():
                 for p in ref_params:
@@ -246,15 +251,21 @@ def main():
                 obs = big.gather(idx)["obs"]
                 torch.autograd.backward([a_ref.actor(obs), a_ref.critic(obs)], [dlogits, dvalue.view(B, 1)])
 
-            ms = timed({"device": device_arm, "torch": torch_arm}, inner=100)
+            ms = timed({"device": device_arm, "torch": torch_arm, "tiled": tiled_arm}, inner=100)
+            same = all(torch.equal(p.grad.view(torch.int32), q.grad.view(torch.int32))
+                       for p, q in zip(a_dev.parameters(), a_tiled.parameters()))
             diff = max(float((p.grad - q.grad).abs().max()) for p, q in zip(a_dev.parameters(), ref_params))
             scale = max(float(q.grad.abs().max()) for q in ref_params)
             passes[f"B{B}"] = {"device_us": round(ms["device"] * 1e3, 1), "torch_us": round(ms["torch"] * 1e3, 1),
+                               "tiled_us": round(ms["tiled"] * 1e3, 1),
                                "ratio_torch_over_device": round(ms["torch"] / ms["device"], 2),
-                               "faster": "device" if ms["device"] < ms["torch"] else "torch",
+                               "ratio_torch_over_tiled": round(ms["torch"] / ms["tiled"], 2),
+                               "ratio_device_over_tiled": round(ms["device"] / ms["tiled"], 2),
+                               "faster": min(ms, key=ms.get), "tiled_gradients_equal_device_bytes": same,
                                "max_abs_gradient_difference_to_torch": diff, "max_abs_gradient": scale}
         passes["note"] = ("forward and backward of both networks for B store positions, fixed dlogits / dvalue: DeviceNets.forward + "
-                          "backward (spl_ppo_net_forward: 1 launch, spl_ppo_net_backward: 3) beside store.gather + actor + critic + "
+                          "backward (spl_ppo_net_forward: 1 launch, spl_ppo_net_backward: 3) and the same with tiled=True "
+                          "(spl_ppo_net_forward_tiled: 3 launches, spl_ppo_net_backward_tiled: 4) beside store.gather + actor + critic + "
                           "torch.autograd.backward from cleared gradients; device events around 100 back-to-back iterations, arms "
                           "alternating, medians")
 
@@ -263,7 +274,7 @@ def main():
                 def run():
                     a = copy.deepcopy(trained)
                     opt = DeviceAdam(list(a.parameters()), lr=2.5e-4, eps=1e-5)
-                    nets = DeviceNets(a) if device_nets else False
+                    nets = DeviceNets(a, tiled=device_nets == "tiled") if device_nets else False
                     g = torch.Generator(device=dev).manual_seed(0)
                     torch.cuda.synchronize(dev)
                     t0 = time.perf_counter()
@@ -273,7 +284,7 @@ def main():
                     return (time.perf_counter() - t0) * 1e3, res
                 return run
 
-            runs = {"torch_nets": arm(False), "device_nets": arm(True)}
+            runs = {"torch_nets": arm(False), "device_nets": arm(True), "tiled_nets": arm("tiled")}
             for fn in runs.values():
                 fn()
             times, last = {k: [] for k in runs}, {}
@@ -287,19 +298,20 @@ def main():
                 out[f"{name}_optimizer_steps"] = last[name]["optimizer_steps"]
             total = store.num_steps * store.num_envs
             out.update({"ratio_torch_over_device": round(out["torch_nets_ms"] / out["device_nets_ms"], 3),
-                        "faster": "device_nets" if out["device_nets_ms"] < out["torch_nets_ms"] else "torch_nets",
+                        "ratio_torch_over_tiled": round(out["torch_nets_ms"] / out["tiled_nets_ms"], 3),
+                        "faster": min(runs, key=lambda name: out[f"{name}_ms"]),
                         "minibatches_run": 4 * -(-total // minibatch), "K": store.num_steps, "T": store.num_envs,
                         "minibatch": minibatch, "epochs": 4})
             return out
 
         updates = {"reference_shape": update_arms(collected(16, 128), 256), "large": update_arms(big, 65536)}
-        updates["note"] = ("one ppo_update(fused_loss=True, target_kl=0.02) with DeviceAdam from the trained checkpoint, without and "
-                           "with device_nets (a DeviceNets built outside the clock, as the optimiser is), host clock from the call to "
+        updates["note"] = ("one ppo_update(fused_loss=True, target_kl=0.02) with DeviceAdam from the trained checkpoint, without "
+                           "device_nets, with them and with DeviceNets(tiled=True) (a DeviceNets built outside the clock, as the optimiser is), host clock from the call to "
                            "a device synchronise behind it, arms alternating, medians")
         section = {"passes": passes, "ppo_update": updates}
         if args.nets_json:
             with open(args.nets_json, "w") as f:
-                json.dump({"metric": "PPO network passes (spl_ppo_net_forward / spl_ppo_net_backward) and whole updates, one MI355X",
+                json.dump({"metric": "PPO network passes (spl_ppo_net_forward / spl_ppo_net_backward and their _tiled forms) and whole updates, one MI355X",
                            "repeats": args.repeats, "nets": section}, f, indent=1)
                 f.write("\n")
         return section
