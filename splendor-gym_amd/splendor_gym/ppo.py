@@ -12,26 +12,58 @@ masks: 2.8 GB instead of 10.4 GB at 128 steps x 65 536 tables):
     into ``ActorCritic.get_action_and_value``'s float32 inputs) and ``minibatches``;
   * ``collect``  num_steps iterations of the config-5 loop (FusedActorCritic.act on the env's compact
     rows, DualStepVectorEnv.dual_step), recorded, and the bootstrap value; eager or one hipGraph;
-  * ``ppo_update``  the update of ppo_splendor.py:327-361 in torch over ``store.minibatches``; with
-    ``fused_loss=True`` its loss head (masked softmax, ratio, clips, means, and their gradients) is
-    ``PPORolloutStore.loss``, one device call on the store's planes;
-  * ``DeviceAdam``  what follows loss.backward() as one device call per minibatch (spl_ppo_adam): the
-    global-norm clip, torch.optim.Adam's step and the target-KL early stop, decided on the device, so that
-    ``ppo_update`` with it reads the device once per update instead of once per minibatch.
+  * ``ppo_update``  the update of ppo_splendor.py:327-361: one loop over ``store.minibatches`` in which a
+    loss head leaves every p.grad and the minibatch's statistics, and an optimiser step consumes them.
 
+The head is torch autograd (the default), ``PPORolloutStore.loss`` behind the two networks (``fused_loss``) or
+``DeviceNets`` (``device_nets``); the step is a torch.optim optimiser or a ``DeviceAdam``; any head goes with either:
+
+  * ``PPORolloutStore.loss``  everything between the two networks and loss.backward() (masked softmax,
+    ratio, clips, means, and their gradients) as one device call on the store's planes (spl_ppo_loss);
   * ``DeviceNets``  the two networks' forward and backward passes as device calls (spl_ppo_net_forward /
     spl_ppo_net_backward) that read the observations from the store by position and write the parameter
-    gradients where the optimiser reads them; ``ppo_update(device_nets=True)`` runs a minibatch as
-    forward -> loss -> backward -> step without autograd.  ``DeviceNets(agent, tiled=True | "auto")`` runs
-    the passes on the LDS-tiled matrix-core kernels built for minibatches of thousands of rows
-    (spl_ppo_net_forward_tiled / spl_ppo_net_backward_tiled), with the same bytes.
+    gradients where the optimiser reads them.  ``DeviceNets(agent, tiled=True | "auto")`` runs the passes on
+    the LDS-tiled matrix-core kernels built for minibatches of thousands of rows
+    (spl_ppo_net_forward_tiled / spl_ppo_net_backward_tiled), with the same bytes;
+  * ``DeviceAdam``  what follows the head as one device call per minibatch (spl_ppo_adam): the global-norm
+    clip, torch.optim.Adam's step and the target-KL early stop, decided on the device, so that
+    ``ppo_update`` with it reads the device once per update instead of once per minibatch.
 
-Without ``device_nets`` the two networks' passes stay in torch.  There is no CPU fallback.
+There is no CPU fallback for the store, ``DeviceAdam`` or ``DeviceNets``.
 """
 import ctypes
 
 from . import _native
 from ._native import NUM_ACTIONS, OBS_DIM, OBS_U8, PpoGae, PpoGather, PpoLoss, PpoLossOut, PpoRecord, check
+
+
+def _tensor(x, what, dtypes, shape, device=None, or_shape=None):
+    """x, if it is a contiguous tensor of one of `dtypes` and of `shape` (None: any; `or_shape`: a second
+    one) on `device` (None: anywhere); otherwise a ValueError that names `what`, what it must be and what
+    it is."""
+    if getattr(x, "dtype", None) in dtypes and (shape is None or x.shape == shape or x.shape == or_shape) and \
+            x.is_contiguous() and (device is None or x.device == device):
+        return x
+    want = f"{dtypes[0]}{'' if shape is None else ' ' + str(list(shape))} tensor{'' if device is None else f' on {device}'}"
+    got = f"{x.dtype} {list(x.shape)} on {x.device}{'' if x.is_contiguous() else ' (not contiguous)'}" \
+        if hasattr(x, "is_contiguous") else f"a {type(x).__name__}"
+    raise ValueError(f"{what} must be a contiguous {want}, not {got}")
+
+
+def _positions(idx, device):
+    """B of the flat positions idx, which must be a non-empty contiguous int64 [B] tensor on `device`."""
+    import torch
+    if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int64 or idx.dim() != 1 or not idx.is_contiguous() or \
+            idx.device != device or idx.numel() < 1:
+        raise ValueError(f"idx must be a non-empty contiguous int64 [B] tensor on {device}")
+    return idx.numel()
+
+
+class _OnDevice:
+    """What the store, DeviceAdam and DeviceNets share: `torch`, `device`, and the stream their calls go to."""
+
+    def _stream(self):
+        return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 
 
 class PPOLossOut:
@@ -74,7 +106,7 @@ def _loss_function(torch):
     return _LOSS_FUNCTION
 
 
-class PPORolloutStore:
+class PPORolloutStore(_OnDevice):
     """Step-major planes of one rollout (num_steps x num_envs), as torch tensors on `device`:
     obs_u8 uint8 [K, T, 300], mask_bits int64 [K, T] (the uint64 words of the ABI), action int32,
     logprob / value / reward / adv / ret float32, done uint8 [K, T]; last_value float32 [T] (the
@@ -107,14 +139,6 @@ class PPORolloutStore:
         self._scratch = z((int(check(self.lib, self.lib.spl_ppo_gae_scratch_bytes(T))) // 8,), torch.float64)
         self._loss_bufs = {}  # B -> the buffers of loss(): scratch, dlogits, dvalue, out, the call serial
 
-    def _stream(self):
-        return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _own(self, x, dtypes, shape, what):
-        if x.dtype not in dtypes or tuple(x.shape) != shape or not x.is_contiguous() or x.device != self.device:
-            raise ValueError(f"{what} must be a contiguous {dtypes[0]} {list(shape)} tensor on {self.device}")
-        return x
-
     def _record(self, **kw):
         with self.torch.cuda.device(self.device):
             check(self.lib, self.lib.spl_ppo_record(self.num_envs, ctypes.byref(PpoRecord(**kw)), self._stream()))
@@ -123,16 +147,16 @@ class PPORolloutStore:
         """Row k's observation (the compact uint8 [T, 300] rows) and legal mask (int8 [T, 45], nonzero =
         legal): call before the dual step that consumes them."""
         t, T = self.torch, self.num_envs
-        self._own(obs_u8, (t.uint8,), (T, OBS_U8), "obs_u8")
-        self._own(mask, (t.int8, t.uint8, t.bool), (T, NUM_ACTIONS), "mask")
+        _tensor(obs_u8, "obs_u8", (t.uint8,), (T, OBS_U8), self.device)
+        _tensor(mask, "mask", (t.int8, t.uint8, t.bool), (T, NUM_ACTIONS), self.device)
         self._record(obs_u8=obs_u8.data_ptr(), dst_obs_u8=self.obs_u8[k].data_ptr(), mask=mask.data_ptr(),
                      dst_mask_bits=self.mask_bits[k].data_ptr())
 
     def record_post(self, k, reward, done):
         """Row k's reward (float32 [T]) and done (one byte per table) as the dual step returned them."""
         t, T = self.torch, self.num_envs
-        self._own(reward, (t.float32,), (T,), "reward")
-        self._own(done, (t.uint8, t.bool, t.int8), (T,), "done")
+        _tensor(reward, "reward", (t.float32,), (T,), self.device)
+        _tensor(done, "done", (t.uint8, t.bool, t.int8), (T,), self.device)
         self._record(reward=reward.data_ptr(), dst_reward=self.reward[k].data_ptr(), done=done.data_ptr(),
                      dst_done=self.done[k].data_ptr())
 
@@ -148,7 +172,7 @@ class PPORolloutStore:
         lv = self.last_value if last_value is None else last_value
         if lv.dim() == 2 and lv.shape[1] == 1:
             lv = lv.view(-1)
-        self._own(lv, (t.float32,), (T,), "last_value")
+        _tensor(lv, "last_value", (t.float32,), (T,), self.device)
         a = PpoGae(reward=self.reward.data_ptr(), value=self.value.data_ptr(), done=self.done.data_ptr(),
                    last_value=lv.data_ptr(), adv=self.adv.data_ptr(), ret=self.ret.data_ptr(), gamma=float(gamma),
                    lam=float(gae_lambda), stats=self._stats.data_ptr(), scratch=self._scratch.data_ptr())
@@ -171,21 +195,18 @@ class PPORolloutStore:
         store's mean32 / std32 on the device when `normalize`.  A position outside the store leaves its
         rows as they were and counts in self.errors."""
         t = self.torch
-        if idx.dtype != t.int64 or idx.dim() != 1 or not idx.is_contiguous() or idx.device != self.device or \
-                idx.numel() < 1:
-            raise ValueError(f"idx must be a non-empty contiguous int64 [B] tensor on {self.device}")
-        B = idx.numel()
+        B = _positions(idx, self.device)
         if out is None:
             e = lambda shape, dt: t.empty(shape, dtype=dt, device=self.device)
             out = {"obs": e((B, OBS_DIM), t.float32), "mask": e((B, NUM_ACTIONS), t.float32), "action": e((B,), t.int64),
                    "logprob": e((B,), t.float32), "value": e((B,), t.float32), "adv": e((B,), t.float32),
                    "ret": e((B,), t.float32)}
         else:
-            self._own(out["obs"], (t.float32,), (B, OBS_DIM), "out['obs']")
-            self._own(out["mask"], (t.float32,), (B, NUM_ACTIONS), "out['mask']")
-            self._own(out["action"], (t.int64,), (B,), "out['action']")
+            _tensor(out["obs"], "out['obs']", (t.float32,), (B, OBS_DIM), self.device)
+            _tensor(out["mask"], "out['mask']", (t.float32,), (B, NUM_ACTIONS), self.device)
+            _tensor(out["action"], "out['action']", (t.int64,), (B,), self.device)
             for name in ("logprob", "value", "adv", "ret"):
-                self._own(out[name], (t.float32,), (B,), f"out['{name}']")
+                _tensor(out[name], f"out['{name}']", (t.float32,), (B,), self.device)
         a = PpoGather(K=self.num_steps, T=self.num_envs, normalize=1 if normalize else 0, reserved=0,
                       idx=idx.data_ptr(), obs_u8=self.obs_u8.data_ptr(), mask_bits=self.mask_bits.data_ptr(),
                       action=self.action.data_ptr(), logprob=self.logprob.data_ptr(), value=self.value.data_ptr(),
@@ -242,12 +263,9 @@ class PPORolloutStore:
         its mask, is a bad row: zero gradients, left out of the means (which still divide by B), counted
         in self.errors and out.bad."""
         t = self.torch
-        if idx.dtype != t.int64 or idx.dim() != 1 or not idx.is_contiguous() or idx.device != self.device or \
-                idx.numel() < 1:
-            raise ValueError(f"idx must be a non-empty contiguous int64 [B] tensor on {self.device}")
-        B = idx.numel()
-        self._own(logits, (t.float32,), (B, NUM_ACTIONS), "logits")
-        self._own(value, (t.float32,), (B, 1) if value.dim() == 2 else (B,), "value")
+        B = _positions(idx, self.device)
+        _tensor(logits, "logits", (t.float32,), (B, NUM_ACTIONS), self.device)
+        _tensor(value, "value", (t.float32,), (B,), self.device, or_shape=(B, 1))
         coef = (float(clip_coef), float(vclip), float(vf_coef), -float(ent_coef) if entropy_bonus else float(ent_coef))
         return _loss_function(t).apply(logits, value, self, idx, coef, bool(normalize)), self._loss_buffers(B)["out"]
 
@@ -361,7 +379,7 @@ def adam_state_of(state_dict, shapes):
     return steps.pop(), ms, vs, g
 
 
-class DeviceAdam:
+class DeviceAdam(_OnDevice):
     """clip_grad_norm_, torch.optim.Adam.step and the target-KL early stop as one device call per minibatch
     (spl_ppo_adam, include/splendor_ppo.h).  The parameters and their gradients stay where torch put them;
     the two moments live in arenas this object owns, and the hyper-parameters, the step count, the gate's
@@ -381,9 +399,9 @@ class DeviceAdam:
             raise ValueError(f"DeviceAdam takes 1 to {_native.PPO_ADAM_MAX_TENSORS} parameter tensors, not {len(self.params)}")
         self.device = self.params[0].device if isinstance(self.params[0], torch.Tensor) else None
         for i, p in enumerate(self.params):
-            if not isinstance(p, torch.Tensor) or p.dtype != torch.float32 or not p.is_contiguous() or p.numel() < 1 or \
-                    p.device != self.device or p.device.type != "cuda":
-                raise ValueError(f"parameter {i} must be a non-empty contiguous float32 tensor on one GPU (no CPU fallback)")
+            _tensor(p, f"parameter {i}", (torch.float32,), None, self.device)
+            if p.numel() < 1 or p.device.type != "cuda":
+                raise ValueError(f"parameter {i} must be a non-empty tensor on a GPU (no CPU fallback)")
         self._at, total = [], 0
         for p in self.params:
             self._at.append(total)
@@ -410,14 +428,9 @@ class DeviceAdam:
         """The two moment arenas: contiguous float32 [arena_floats] on the device, segment i at the sum of the
         earlier segments' sizes, each rounded up to a multiple of 4."""
         for x in (exp_avg, exp_avg_sq):
-            if x.dtype != self.torch.float32 or tuple(x.shape) != (self.arena_floats,) or not x.is_contiguous() or \
-                    x.device != self.device:
-                raise ValueError(f"an arena must be a contiguous float32 [{self.arena_floats}] tensor on {self.device}")
+            _tensor(x, "an arena", (self.torch.float32,), (self.arena_floats,), self.device)
         self._exp_avg, self._exp_avg_sq = exp_avg, exp_avg_sq
         self._args.exp_avg, self._args.exp_avg_sq = exp_avg.data_ptr(), exp_avg_sq.data_ptr()
-
-    def _stream(self):
-        return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 
     def _set(self, field, value, integer=False):
         """One asynchronous small write into the state block (a captured step() reads the block, so it
@@ -469,8 +482,7 @@ class DeviceAdam:
             g = p.grad
             if g is None:
                 raise ValueError(f"parameter {i} has no gradient")
-            if g.dtype != t.float32 or not g.is_contiguous() or g.shape != p.shape or g.device != self.device:
-                raise ValueError(f"the gradient of parameter {i} must be a contiguous float32 tensor of its shape on {self.device}")
+            _tensor(g, f"the gradient of parameter {i}", (t.float32,), p.shape, self.device)
             a.param[i], a.grad[i] = p.data_ptr(), g.data_ptr()
         if approx_kl is not None:
             if not isinstance(approx_kl, t.Tensor) or approx_kl.numel() != 1 or approx_kl.device != self.device or \
@@ -527,7 +539,7 @@ class DeviceAdam:
         self.set_eps(group["eps"])
 
 
-class DeviceNets:
+class DeviceNets(_OnDevice):
     """The actor's and the critic's forward and backward passes of the update as device calls
     (spl_ppo_net_forward / spl_ppo_net_backward, include/splendor_ppo.h): no autograd graph, no gathered
     float observations, no zero_grad.  `agent` is an ActorCritic whose twelve parameters are float32,
@@ -563,9 +575,7 @@ class DeviceNets:
             H = _native.PPO_NET_HIDDEN
             shapes = ((H, OBS_DIM), (H,), (H, H), (H,), (n3, H), (n3,))
             for p, shape, field in zip(ps, shapes, ("w1", "b1", "w2", "b2", "w3", "b3")):
-                if p.dtype != torch.float32 or not p.is_contiguous() or tuple(p.shape) != shape:
-                    raise ValueError(f"{name}.{field} must be a contiguous float32 {list(shape)} tensor, not "
-                                     f"{p.dtype} {list(p.shape)}{'' if p.is_contiguous() else ' (not contiguous)'}")
+                _tensor(p, f"{name}.{field}", (torch.float32,), shape)  # wherever it lies: the device is checked below
             nets.append(ps)
         self.torch, self.lib = _native.require_gpu(), _native.load_library()
         self.params = nets[0] + nets[1]  # the actor's six, then the critic's
@@ -585,9 +595,6 @@ class DeviceNets:
     def _use_tiled(self, B):
         return self.tiled is True or (self.tiled == "auto" and B >= self.TILED_MIN_ROWS)
 
-    def _stream(self):
-        return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
-
     def _mlp(self, tensors):
         return _native.PpoMlp(*(x.data_ptr() for x in tensors))
 
@@ -603,13 +610,9 @@ class DeviceNets:
         return bufs
 
     def _idx(self, store, idx):
-        t = self.torch
         if store.device != self.device:
             raise ValueError(f"the store must be on {self.device}")
-        if not isinstance(idx, t.Tensor) or idx.dtype != t.int64 or idx.dim() != 1 or not idx.is_contiguous() or \
-                idx.device != self.device or idx.numel() < 1:
-            raise ValueError(f"idx must be a non-empty contiguous int64 [B] tensor on {self.device}")
-        if idx.numel() > self.MAX_ROWS:
+        if _positions(idx, self.device) > self.MAX_ROWS:
             raise ValueError(f"DeviceNets takes at most {self.MAX_ROWS} rows a call (SPL_PPO_NET_MAX_ROWS), not {idx.numel()}")
         return idx if idx.data_ptr() % 16 == 0 else idx.clone()  # a slice of a permutation may start anywhere
 
@@ -640,15 +643,13 @@ class DeviceNets:
         if B not in self._bufs:
             raise ValueError(f"backward() needs a forward() with the same B = {B} before it")
         bufs = self._bufs[B]
-        for x, shapes, what in ((dlogits, ((B, NUM_ACTIONS),), "dlogits"), (dvalue, ((B,), (B, 1)), "dvalue")):
-            if not isinstance(x, t.Tensor) or x.dtype != t.float32 or tuple(x.shape) not in shapes or not x.is_contiguous() or \
-                    x.device != self.device:
-                raise ValueError(f"{what} must be a contiguous float32 {list(shapes[0])} tensor on {self.device}")
+        _tensor(dlogits, "dlogits", (t.float32,), (B, NUM_ACTIONS), self.device)
+        _tensor(dvalue, "dvalue", (t.float32,), (B,), self.device, or_shape=(B, 1))
         for p, g in zip(self.params, self._grads):
             if p.grad is None:
                 p.grad = g
-            elif p.grad.dtype != t.float32 or not p.grad.is_contiguous() or p.grad.shape != p.shape or p.grad.device != self.device:
-                raise ValueError("every p.grad must be a contiguous float32 tensor of its parameter's shape on the device")
+            else:
+                _tensor(p.grad, "every p.grad", (t.float32,), p.shape, self.device)
         grads = [p.grad for p in self.params]
         a = _native.PpoNetBwd(K=store.num_steps, T=store.num_envs, reserved=0, idx=idx.data_ptr(),
                               obs_u8=store.obs_u8.data_ptr(), actor=self._mlp(self.params[:6]),
@@ -659,6 +660,87 @@ class DeviceNets:
             call = self.lib.spl_ppo_net_backward_tiled if self._use_tiled(B) else self.lib.spl_ppo_net_backward
             check(self.lib, call(B, ctypes.byref(a), self._stream()))
         bufs["idx"] = idx
+
+
+class _Lazy:
+    """Attributes given as functions without arguments, each evaluated when it is first read, and kept."""
+
+    def __init__(self, **thunks):
+        self._thunks = thunks
+
+    def __getattr__(self, name):
+        if name == "_thunks" or name not in self._thunks:
+            raise AttributeError(name)
+        setattr(self, name, self._thunks.pop(name)())
+        return getattr(self, name)
+
+
+def _result(stat, first_kl, steps, with_clipfrac, **more):
+    """ppo_update's dictionary; stat(name): the last applied minibatch's statistic as a Python number."""
+    res = {name: stat(name) for name in ("policy_loss", "value_loss", "entropy", "approx_kl")}
+    res.update(first_approx_kl=float(first_kl), optimizer_steps=steps)
+    if with_clipfrac:
+        res["clipfrac"] = stat("clipfrac")
+    return {**res, **more}
+
+
+class _TorchOptimStep:
+    """ppo_update's step with a torch.optim optimiser: clip_grad_norm_, step() and, with a target, one read of the
+    minibatch's KL.  step(out) says whether the epoch goes on."""
+    begin_epoch = staticmethod(lambda: None)
+
+    def __init__(self, torch, agent, optimizer, max_grad_norm, target_kl):
+        self.clip = lambda: torch.nn.utils.clip_grad_norm_(agent.parameters(), max_grad_norm)
+        self.optimizer, self.zero_grad, self.target_kl = optimizer, optimizer.zero_grad, target_kl
+        self.first_kl, self.last, self.steps = None, None, 0
+
+    def step(self, out):
+        self.clip()
+        self.optimizer.step()
+        self.steps += 1
+        kl = out.approx_kl  # the torch head's is worked out here, behind the step, whether or not anything reads it
+        if self.first_kl is None:  # a PPOLossOut's views follow the next call with the same B
+            self.first_kl = kl.clone() if isinstance(out, PPOLossOut) else kl
+        self.last = out  # read after the loop, when a PPOLossOut holds the latest call with its B: this one
+        return not (self.target_kl > 0 and kl.item() > self.target_kl)
+
+    def result(self):
+        return _result(lambda name: float(getattr(self.last, name)), self.first_kl, self.steps,
+                       isinstance(self.last, PPOLossOut))
+
+
+class _DeviceAdamStep:
+    """ppo_update's step with a DeviceAdam: the clip, the step and the early stop in DeviceAdam.step, fed the
+    minibatch's statistics; nothing is read inside the loop, the optimiser's state once for the result."""
+    zero_grad = staticmethod(lambda: None)  # DeviceAdam.step takes the gradients: every p.grad is None by now
+
+    def __init__(self, optimizer, max_grad_norm, target_kl):
+        norm = -1.0 if max_grad_norm is None else float(max_grad_norm)
+        if optimizer.max_grad_norm != norm:
+            optimizer.set_max_grad_norm(norm)
+        if optimizer.target_kl != float(target_kl):
+            optimizer.set_target_kl(target_kl)
+        self.optimizer, self.epochs, self.with_clipfrac = optimizer, 0, False
+
+    def begin_epoch(self):
+        (self.optimizer.begin_epoch if self.epochs else self.optimizer.begin_update)()
+        self.epochs += 1
+
+    def step(self, out):
+        self.with_clipfrac = isinstance(out, PPOLossOut)
+        if not self.with_clipfrac:  # the torch head's statistics as one spl_ppo_loss_out_t for the optimiser's latches
+            torch = self.optimizer.torch
+            stats = [getattr(out, name) for name in PPOLossOut.STATS]
+            buf = torch.zeros(ctypes.sizeof(PpoLossOut) // 8, dtype=torch.float64, device=self.optimizer.device)
+            buf[:len(stats)] = torch.stack(stats)
+            out = PPOLossOut(buf, torch)
+        self.optimizer.step(loss_out=out)
+        return True  # the device skips the steps behind the crossing; the host runs every minibatch
+
+    def result(self):
+        st = self.optimizer.read_state()
+        return _result(st["last"].__getitem__, st["first"]["approx_kl"], st["applied"], self.with_clipfrac,
+                       gated=st["gated"], grad_norm=st["grad_norm"])
 
 
 def ppo_update(agent, optimizer, store, clip_coef=0.2, vclip=0.2, ent_coef=0.03, vf_coef=0.5, update_epochs=4,
@@ -672,192 +754,84 @@ def ppo_update(agent, optimizer, store, clip_coef=0.2, vclip=0.2, ent_coef=0.03,
     (entropy_loss = -entropy; ... + ent_coef * (-entropy_loss)) ADDS the entropy to the minimised loss.
     That is reproduced by default; entropy_bonus=True subtracts it instead (the usual PPO bonus).
 
+    A minibatch is a loss head, which leaves every p.grad and the statistics, then an optimiser step.
+
+    The head.  By default store.gather, agent.get_action_and_value, the loss in torch and backward().
     fused_loss=True replaces everything between the two networks and loss.backward() by store.loss (one
     device call for the loss, its statistics and its gradients); the gather then only supplies the
-    observations.  The arithmetic is the same, in another summation order.
+    observations.  The arithmetic is the same, in another summation order.  device_nets=True (or a DeviceNets
+    over this agent, which keeps its buffers from update to update) also moves the two networks' passes to
+    the device and implies the fused loss: DeviceNets.forward -> the loss launch -> DeviceNets.backward, with
+    no autograd, no gather and no zero_grad.
+
+    The step.  A torch.optim optimiser: zero_grad, clip_grad_norm_, step() and the per-minibatch KL
+    read-back.  A DeviceAdam: the norm clip, the Adam step and the early stop are one device call per
+    minibatch (DeviceAdam.step, fed the minibatch's KL), with any head: no clip_grad_norm_, no zero_grad and
+    no read-back inside the loop, and one synchronising read of the optimiser's state at the end (with the
+    nets head: four device calls a minibatch and one read-back per update).  max_grad_norm and target_kl are
+    this call's arguments: the optimiser's own are set to them when they differ.  Since the host no longer
+    learns that the KL crossed the line, it runs every minibatch of every epoch, and a minibatch behind the
+    crossing still pays for its head before its step is skipped on the device: the price of not synchronising.
 
     Returns the last minibatch's policy_loss, value_loss, entropy and approx_kl, first_approx_kl (the
-    first minibatch's, evaluated before any optimiser step) and the number of optimiser steps; with
-    fused_loss also the last minibatch's clipfrac.
-
-    optimizer may be a DeviceAdam.  Then the norm clip, the Adam step and the early stop are one device call
-    per minibatch (DeviceAdam.step, fed the minibatch's KL), with either loss head: no clip_grad_norm_, no
-    zero_grad and no read-back inside the loop, and one synchronising read of the optimiser's state at the
-    end.  max_grad_norm and target_kl are this call's arguments: the optimiser's own are set to them when
-    they differ.  Since the host no longer learns that the KL crossed the line, it runs every minibatch of
-    every epoch, and a minibatch behind the crossing still pays for its forward and backward pass before
-    its step is skipped on the device: the price of not synchronising.  The dictionary is the same, filled
-    from the device (optimizer_steps = the applied steps, the statistics those of the last applied step,
-    first_approx_kl that of the first), plus gated (skipped minibatches) and grad_norm (the last call's).
-
-    device_nets=True (or a DeviceNets over this agent, which keeps its buffers from update to update) also
-    moves the two networks' passes to the device and implies the fused loss head: a minibatch is
-    DeviceNets.forward -> the loss launch -> DeviceNets.backward -> optimizer.step, with no autograd, no gather
-    and no zero_grad.  With a DeviceAdam that is four device calls and one read-back per update; with a
-    torch.optim optimiser clip_grad_norm_, step() and the per-minibatch KL read-back stay.  The dictionary is
-    that of the same optimiser's fused-loss path."""
+    first minibatch's, evaluated before any optimiser step) and optimizer_steps; with the fused or the nets
+    head also the last minibatch's clipfrac.  With a DeviceAdam the dictionary is filled from the device
+    (optimizer_steps = the applied steps, the statistics those of the last applied step, first_approx_kl
+    that of the first), plus gated (skipped minibatches) and grad_norm (the last call's)."""
     torch = store.torch
+    if int(update_epochs) < 1:
+        raise ValueError("update_epochs must be at least 1")
+    nets = None
     if device_nets is not False and device_nets is not None:
         nets = device_nets if isinstance(device_nets, DeviceNets) else DeviceNets(agent)
-        return _ppo_update_nets(agent, nets, optimizer, store, clip_coef, vclip, ent_coef, vf_coef, update_epochs,
-                                minibatch_size, target_kl, max_grad_norm, generator, entropy_bonus)
+        if nets.params[0] is not agent.actor[0].weight or nets.params[6] is not agent.critic[0].weight:
+            raise ValueError("device_nets was built over another agent's parameters")
     if isinstance(optimizer, DeviceAdam):
-        return _ppo_update_device(agent, optimizer, store, clip_coef, vclip, ent_coef, vf_coef, update_epochs,
-                                  minibatch_size, target_kl, max_grad_norm, generator, entropy_bonus, fused_loss)
-    if fused_loss:
-        return _ppo_update_fused(agent, optimizer, store, clip_coef, vclip, ent_coef, vf_coef, update_epochs,
-                                 minibatch_size, target_kl, max_grad_norm, generator, entropy_bonus)
-    last, first_kl, steps = None, None, 0
-    sign = -1.0 if entropy_bonus else 1.0
-    for _ in range(int(update_epochs)):
-        for idx in store.minibatches(minibatch_size, generator):
-            mb = store.gather(idx, normalize=True)
-            _, new_logprob, entropy, new_value = agent.get_action_and_value(mb["obs"], mb["mask"], mb["action"])
-            ratio = (new_logprob - mb["logprob"]).exp()
-            clip_adv = torch.clamp(ratio, 1 - clip_coef, 1 + clip_coef) * mb["adv"]
-            policy_loss = -torch.min(ratio * mb["adv"], clip_adv).mean()
-            v_pred = new_value.squeeze(-1)
-            v_clipped = mb["value"] + torch.clamp(v_pred - mb["value"], -vclip, vclip)
-            value_loss = 0.5 * torch.max((v_pred - mb["ret"]).pow(2), (v_clipped - mb["ret"]).pow(2)).mean()
-            entropy = entropy.mean()
-            loss = policy_loss + vf_coef * value_loss + sign * ent_coef * entropy
-            optimizer.zero_grad()
-            loss.backward()
-            torch.nn.utils.clip_grad_norm_(agent.parameters(), max_grad_norm)
-            optimizer.step()
-            steps += 1
-            approx_kl = (mb["logprob"] - new_logprob).mean().detach()
-            if first_kl is None:
-                first_kl = approx_kl
-            last = (policy_loss.detach(), value_loss.detach(), entropy.detach(), approx_kl)
-            if target_kl > 0 and approx_kl.item() > target_kl:
-                break
-    if last is None:
-        raise ValueError("update_epochs must be at least 1")
-    vals = [float(x) for x in last]
-    return {"policy_loss": vals[0], "value_loss": vals[1], "entropy": vals[2], "approx_kl": vals[3],
-            "first_approx_kl": float(first_kl), "optimizer_steps": steps}
-
-
-def _ppo_update_fused(agent, optimizer, store, clip_coef, vclip, ent_coef, vf_coef, update_epochs, minibatch_size,
-                      target_kl, max_grad_norm, generator, entropy_bonus):
-    """ppo_update(fused_loss=True): the same loop with store.loss as the loss head."""
-    torch = store.torch
-    last, first_kl, steps = None, None, 0
-    for _ in range(int(update_epochs)):
-        for idx in store.minibatches(minibatch_size, generator):
-            obs = store.gather(idx, normalize=True)["obs"]
-            loss, out = store.loss(idx, agent.actor(obs), agent.critic(obs), clip_coef=clip_coef, vclip=vclip,
-                                   vf_coef=vf_coef, ent_coef=ent_coef, entropy_bonus=entropy_bonus, normalize=True)
-            optimizer.zero_grad()
-            loss.backward()
-            torch.nn.utils.clip_grad_norm_(agent.parameters(), max_grad_norm)
-            optimizer.step()
-            steps += 1
-            if first_kl is None:
-                first_kl = out.approx_kl.clone()
-            last = out  # its views hold the latest call with this B, which is this one when the loop ends
-            if target_kl > 0 and out.approx_kl.item() > target_kl:
-                break
-    if last is None:
-        raise ValueError("update_epochs must be at least 1")
-    res = {name: float(getattr(last, name)) for name in ("policy_loss", "value_loss", "entropy", "approx_kl")}
-    return {**res, "first_approx_kl": float(first_kl), "optimizer_steps": steps, "clipfrac": float(last.clipfrac)}
-
-
-def _ppo_update_nets(agent, nets, optimizer, store, clip_coef, vclip, ent_coef, vf_coef, update_epochs, minibatch_size,
-                     target_kl, max_grad_norm, generator, entropy_bonus):
-    """ppo_update(device_nets=...): the same minibatches; forward, loss head and backward as device calls."""
-    torch = store.torch
-    if int(update_epochs) < 1:
-        raise ValueError("update_epochs must be at least 1")
-    if nets.params[0] is not agent.actor[0].weight or nets.params[6] is not agent.critic[0].weight:
-        raise ValueError("device_nets was built over another agent's parameters")
-    on_device = isinstance(optimizer, DeviceAdam)
-    if on_device:
-        norm = -1.0 if max_grad_norm is None else float(max_grad_norm)
-        if optimizer.max_grad_norm != norm:
-            optimizer.set_max_grad_norm(norm)
-        if optimizer.target_kl != float(target_kl):
-            optimizer.set_target_kl(target_kl)
-        optimizer.begin_update()
+        stepper = _DeviceAdamStep(optimizer, max_grad_norm, target_kl)
+    else:
+        stepper = _TorchOptimStep(torch, agent, optimizer, max_grad_norm, target_kl)
     coef = (float(clip_coef), float(vclip), float(vf_coef), -float(ent_coef) if entropy_bonus else float(ent_coef))
-    last, first_kl, steps = None, None, 0
-    for epoch in range(int(update_epochs)):
-        if on_device and epoch:
-            optimizer.begin_epoch()
+
+    def torch_head(idx):
+        mb = store.gather(idx, normalize=True)
+        _, new_logprob, entropy, new_value = agent.get_action_and_value(mb["obs"], mb["mask"], mb["action"])
+        ratio = (new_logprob - mb["logprob"]).exp()
+        clip_adv = torch.clamp(ratio, 1 - clip_coef, 1 + clip_coef) * mb["adv"]
+        policy_loss = -torch.min(ratio * mb["adv"], clip_adv).mean()
+        v_pred = new_value.squeeze(-1)
+        v_clipped = mb["value"] + torch.clamp(v_pred - mb["value"], -vclip, vclip)
+        value_loss = 0.5 * torch.max((v_pred - mb["ret"]).pow(2), (v_clipped - mb["ret"]).pow(2)).mean()
+        entropy = entropy.mean()
+        loss = policy_loss + vf_coef * value_loss + coef[3] * entropy
+        stepper.zero_grad()
+        loss.backward()
+        # PPOLossOut's names.  The KL and the clipfrac are launched when read: a torch.optim step reads the KL behind
+        # its step() and never the clipfrac, a DeviceAdam reads both before its own
+        return _Lazy(loss=loss.detach, policy_loss=policy_loss.detach, value_loss=value_loss.detach, entropy=entropy.detach,
+                     approx_kl=lambda: (mb["logprob"] - new_logprob.detach()).mean(),
+                     clipfrac=lambda: ((ratio.detach() - 1).abs() > clip_coef).float().mean())
+
+    held = []  # the fused head's observations and loss outlive its call, as they would in a flat loop: with both freed
+    # at once an update of 65 536-row minibatches measured 0.2 to 0.5 % slower (the same kernels at other addresses)
+
+    def fused_head(idx):
+        obs = store.gather(idx, normalize=True)["obs"]
+        loss, out = store.loss(idx, agent.actor(obs), agent.critic(obs), *coef, normalize=True)
+        stepper.zero_grad()
+        loss.backward()
+        held[:] = obs, loss
+        return out
+
+    def nets_head(idx):
+        logits, value = nets.forward(store, idx)
+        bufs = store._launch_loss(idx, logits, value, coef, True)
+        nets.backward(store, idx, bufs["dlogits"], bufs["dvalue"])  # overwrites every p.grad: no zero_grad
+        return bufs["out"]
+
+    head = nets_head if nets is not None else fused_head if fused_loss else torch_head
+    for _ in range(int(update_epochs)):
+        stepper.begin_epoch()
         for idx in store.minibatches(minibatch_size, generator):
-            logits, value = nets.forward(store, idx)
-            bufs = store._launch_loss(idx, logits, value, coef, True)
-            nets.backward(store, idx, bufs["dlogits"], bufs["dvalue"])
-            out = bufs["out"]
-            if on_device:
-                optimizer.step(loss_out=out)
-                continue
-            torch.nn.utils.clip_grad_norm_(agent.parameters(), max_grad_norm)
-            optimizer.step()
-            steps += 1
-            if first_kl is None:
-                first_kl = out.approx_kl.clone()
-            last = out
-            if target_kl > 0 and out.approx_kl.item() > target_kl:
+            if not stepper.step(head(idx)):
                 break
-    if on_device:
-        st = optimizer.read_state()
-        last = st["last"]
-        res = {name: last[name] for name in ("policy_loss", "value_loss", "entropy", "approx_kl")}
-        res.update(first_approx_kl=st["first"]["approx_kl"], optimizer_steps=st["applied"], clipfrac=last["clipfrac"])
-        return {**res, "gated": st["gated"], "grad_norm": st["grad_norm"]}
-    res = {name: float(getattr(last, name)) for name in ("policy_loss", "value_loss", "entropy", "approx_kl")}
-    return {**res, "first_approx_kl": float(first_kl), "optimizer_steps": steps, "clipfrac": float(last.clipfrac)}
-
-
-def _ppo_update_device(agent, optimizer, store, clip_coef, vclip, ent_coef, vf_coef, update_epochs, minibatch_size,
-                       target_kl, max_grad_norm, generator, entropy_bonus, fused_loss):
-    """ppo_update with a DeviceAdam: the same minibatches and the same loss (either head), the optimiser's
-    part and the early stop on the device, one read-back at the end."""
-    torch = store.torch
-    if int(update_epochs) < 1:
-        raise ValueError("update_epochs must be at least 1")
-    norm = -1.0 if max_grad_norm is None else float(max_grad_norm)
-    if optimizer.max_grad_norm != norm:
-        optimizer.set_max_grad_norm(norm)
-    if optimizer.target_kl != float(target_kl):
-        optimizer.set_target_kl(target_kl)
-    sign = -1.0 if entropy_bonus else 1.0
-    optimizer.begin_update()
-    for epoch in range(int(update_epochs)):
-        if epoch:
-            optimizer.begin_epoch()
-        for idx in store.minibatches(minibatch_size, generator):
-            if fused_loss:
-                obs = store.gather(idx, normalize=True)["obs"]
-                loss, out = store.loss(idx, agent.actor(obs), agent.critic(obs), clip_coef=clip_coef, vclip=vclip,
-                                       vf_coef=vf_coef, ent_coef=ent_coef, entropy_bonus=entropy_bonus, normalize=True)
-                loss.backward()
-            else:
-                mb = store.gather(idx, normalize=True)
-                _, new_logprob, entropy, new_value = agent.get_action_and_value(mb["obs"], mb["mask"], mb["action"])
-                ratio = (new_logprob - mb["logprob"]).exp()
-                clip_adv = torch.clamp(ratio, 1 - clip_coef, 1 + clip_coef) * mb["adv"]
-                policy_loss = -torch.min(ratio * mb["adv"], clip_adv).mean()
-                v_pred = new_value.squeeze(-1)
-                v_clipped = mb["value"] + torch.clamp(v_pred - mb["value"], -vclip, vclip)
-                value_loss = 0.5 * torch.max((v_pred - mb["ret"]).pow(2), (v_clipped - mb["ret"]).pow(2)).mean()
-                entropy = entropy.mean()
-                loss = policy_loss + vf_coef * value_loss + sign * ent_coef * entropy
-                loss.backward()
-                with torch.no_grad():  # the statistics as one spl_ppo_loss_out_t for the optimiser's latches
-                    approx_kl = (mb["logprob"] - new_logprob).mean()
-                    clipfrac = ((ratio - 1).abs() > clip_coef).float().mean()
-                    buf = torch.zeros(ctypes.sizeof(PpoLossOut) // 8, dtype=torch.float64, device=store.device)
-                    buf[:6] = torch.stack([loss, policy_loss, value_loss, entropy, approx_kl, clipfrac])
-                    out = PPOLossOut(buf, torch)
-            optimizer.step(loss_out=out)
-    st = optimizer.read_state()
-    last = st["last"]
-    res = {name: last[name] for name in ("policy_loss", "value_loss", "entropy", "approx_kl")}
-    res.update(first_approx_kl=st["first"]["approx_kl"], optimizer_steps=st["applied"])
-    if fused_loss:
-        res["clipfrac"] = last["clipfrac"]
-    return {**res, "gated": st["gated"], "grad_norm": st["grad_norm"]}
+    return stepper.result()

@@ -125,7 +125,7 @@ def main(argv=None):
                          ent_coef=args.ent_coef + (args.ent_coef_final - args.ent_coef) * progress,
                          vf_coef=args.vf_coef, update_epochs=args.update_epochs, minibatch_size=args.minibatch_size,
                          target_kl=args.target_kl, generator=gen, entropy_bonus=args.entropy_bonus,
-                         fused_loss=args.fused_loss or args.device_nets, device_nets=nets)
+                         fused_loss=args.fused_loss, device_nets=nets)
         agent_k.refresh()
         pool.refresh()
         if (update + 1) % max(1, args.snapshot_every_updates) == 0:

@@ -484,22 +484,51 @@ def update_f64(agent, store, epochs, minibatch, target_kl, seed=0):
     return list(a.parameters()), kls, len(kls)
 
 
-def run_update(agent, store, device_adam, target_kl, fused_loss=True):
+def run_update(agent, store, device_adam, target_kl, **switches):
+    """ppo_update on a copy of the agent, two epochs of minibatches of 64 from generator seed 0, with either optimiser.
+    switches: ppo_update's own (fused_loss=True unless given), or tiled=... for a DeviceNets(copy, tiled=...) as
+    device_nets.  Returns the parameters, the dictionary and the optimiser."""
     import torch
-    from splendor_gym.ppo import DeviceAdam, ppo_update
+    from splendor_gym.ppo import DeviceAdam, DeviceNets, ppo_update
     a = copy.deepcopy(agent)
     make = DeviceAdam if device_adam else torch.optim.Adam
     opt = make(list(a.parameters()), lr=LR, eps=EPS)
     gen = torch.Generator(device=DEV).manual_seed(0)
-    res = ppo_update(a, opt, store, update_epochs=2, minibatch_size=64, target_kl=target_kl, generator=gen, fused_loss=fused_loss)
+    switches.setdefault("fused_loss", True)
+    if "tiled" in switches:
+        switches["device_nets"] = DeviceNets(a, tiled=switches.pop("tiled"))
+    res = ppo_update(a, opt, store, update_epochs=2, minibatch_size=64, target_kl=target_kl, generator=gen, **switches)
     return list(a.parameters()), res, opt
 
 
 @pytest.fixture(scope="module")
 def reference_update(collected):
-    """The float64 update without a gate, shared by the tests below (nothing changes it)."""
+    """The float64 update without a gate, shared by the tests below and by those of test_gpu_ppo_net.py (nothing
+    changes it)."""
     agent, store = collected
     return update_f64(agent, store, 2, 64, 0.0)
+
+
+def choose_target_kl(agent, store, kls):
+    """target_kl: a midpoint between two neighbours among the ungated run's own minibatch KLs, chosen by the float64
+    loop with `break`: of the midpoints from which every KL of the gated float64 run stays well away, the one that
+    stops it earliest.  Returns the count the float64 loop stops at, the target and e32.
+
+    float32 KLs must fall on the float64 ones' side of the target: the margin is set against the float32 torch
+    path's own distance from the float64 loop (e32), measured on the ungated run's last minibatch."""
+    e32 = abs(run_update(agent, store, False, 0.0)[1]["approx_kl"] - kls[-1])
+    print(f"minibatch KLs {['%.3e' % k for k in kls]}; float32 torch path against the float64 loop, last KL: {e32:.3e}")
+    s, best = sorted(kls), None
+    for a, b in zip(s, s[1:]):
+        if a + b > 0:
+            target = (a + b) / 2
+            _, ran, n = update_f64(agent, store, 2, 64, target)
+            margin = min(abs(k - target) for k in ran)
+            print(f"target {target:.3e}: the float64 loop takes {n} steps, nearest KL {margin:.3e} away")
+            if margin > 100 * e32 and margin > 1e-3 * target and (best is None or n < best[0]):
+                best = (n, target)
+    assert best is not None and best[0] < 8  # the gate acts
+    return best[0], best[1], e32
 
 
 def test_ppo_update_with_the_optimiser_on_the_device(collected, reference_update):
@@ -527,26 +556,10 @@ def test_ppo_update_with_the_optimiser_on_the_device(collected, reference_update
 
 
 def test_ppo_update_stops_where_the_torch_path_stops(collected, reference_update):
-    """target_kl: a midpoint between two neighbours among the ungated run's own minibatch KLs, chosen by the float64
-    loop with `break`: of the midpoints from which every KL of the gated float64 run stays well away, the one that
-    stops it earliest.  Both optimisers must stop at the count the float64 loop stops at."""
+    """With choose_target_kl's target both optimisers must stop at the count the float64 loop stops at."""
     agent, store = collected
     _, kls, _ = reference_update
-    # float32 KLs must fall on the float64 ones' side of the target: the margin is set against the float32 torch
-    # path's own distance from the float64 loop, measured on the ungated run's last minibatch
-    e32 = abs(run_update(agent, store, False, 0.0)[1]["approx_kl"] - kls[-1])
-    print(f"minibatch KLs {['%.3e' % k for k in kls]}; float32 torch path against the float64 loop, last KL: {e32:.3e}")
-    s, best = sorted(kls), None
-    for a, b in zip(s, s[1:]):
-        if a + b > 0:
-            target = (a + b) / 2
-            _, ran, n = update_f64(agent, store, 2, 64, target)
-            margin = min(abs(k - target) for k in ran)
-            print(f"target {target:.3e}: the float64 loop takes {n} steps, nearest KL {margin:.3e} away")
-            if margin > 100 * e32 and margin > 1e-3 * target and (best is None or n < best[0]):
-                best = (n, target)
-    assert best is not None and best[0] < 8  # the gate acts
-    want_steps, target = best
+    want_steps, target, e32 = choose_target_kl(agent, store, kls)
     _, res_dev, opt = run_update(agent, store, True, target)
     _, res_ref, _ = run_update(agent, store, False, target)
     assert res_dev["optimizer_steps"] == res_ref["optimizer_steps"] == want_steps
@@ -554,21 +567,29 @@ def test_ppo_update_stops_where_the_torch_path_stops(collected, reference_update
     assert abs(res_dev["approx_kl"] - res_ref["approx_kl"]) <= 100 * e32 + 1e-3 * target  # the same last applied minibatch
 
 
-def test_cli_device_adam():
-    """python -m splendor_gym.scripts.ppo_device --device-adam --fused-loss at a toy size in a child process:
-    two updates, exit 0, every printed figure finite."""
+def run_cli(*flags, updates):
+    """python -m splendor_gym.scripts.ppo_device with `flags` at a toy size (64 tables x 4 steps, minibatches of 128,
+    `updates` updates from the committed checkpoint) in a child process: exit 0; returns the printed update lines."""
     here = os.path.dirname(os.path.abspath(__file__))
     pkg = os.path.join(os.path.dirname(here), "splendor-gym_amd")
     env = dict(os.environ, PYTHONPATH=os.pathsep.join([pkg] + [x for x in (os.environ.get("PYTHONPATH"),) if x]))
     r = subprocess.run([sys.executable, "-m", "splendor_gym.scripts.ppo_device", "--num-envs", "64", "--num-steps", "4",
-                        "--total-timesteps", str(2 * 64 * 4), "--minibatch-size", "128", "--update-epochs", "2", "--pool-size", "2",
-                        "--fused-loss", "--device-adam", "--lr-anneal", "--load-path",
-                        os.path.join(here, "golden", "ppo_splendor_latest.safetensors")],
+                        "--total-timesteps", str(updates * 64 * 4), "--minibatch-size", "128", "--pool-size", "2", *flags,
+                        "--load-path", os.path.join(here, "golden", "ppo_splendor_latest.safetensors")],
                        env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("update ")]
-    assert len(lines) == 2 and lines[-1].startswith("update 2/2 steps 512 "), r.stdout[-2000:]
-    for ln in lines:
-        nums = re.findall(r"(?:pl|vl|ent|kl) ([-+0-9.einfa]+)", ln)
-        assert len(nums) == 4 and all(np.isfinite(float(x)) for x in nums), ln
-        assert 1 <= int(re.search(r"opt-steps (\d+)", ln).group(1)) <= 4, ln
+    assert len(lines) == updates and lines[-1].startswith(f"update {updates}/{updates} steps {updates * 256} "), r.stdout[-2000:]
+    return lines
+
+
+def finite_figures(line, most_steps):
+    nums = re.findall(r"(?:pl|vl|ent|kl) ([-+0-9.einfa]+)", line)
+    assert len(nums) == 4 and all(np.isfinite(float(x)) for x in nums), line
+    assert 1 <= int(re.search(r"opt-steps (\d+)", line).group(1)) <= most_steps, line
+
+
+def test_cli_device_adam():
+    """ppo_device --device-adam --fused-loss: two updates, every printed figure finite."""
+    for ln in run_cli("--update-epochs", "2", "--fused-loss", "--device-adam", "--lr-anneal", updates=2):
+        finite_figures(ln, 4)

@@ -8,14 +8,12 @@ summation order and in their tanh, so against the float64 oracle a kernel result
 max(4 x torch's float32 error on the same inputs, 64 x 2^-24 x the largest magnitude of the oracle's tensor),
 per tensor: logits, value and B x each of the twelve gradients.  Measured on an MI355X: DESIGN.md's table."""
 import copy
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from test_gpu_ppo_adam import EPS, LR, bits, compare, run_update, update_f64
+from test_gpu_ppo_adam import (EPS, LR, bits, choose_target_kl, compare, finite_figures, reference_update,  # noqa: F401
+                               run_cli, run_update)
 from test_gpu_ppo_loss import DEV, allowed, collected, head_gradients, trained  # noqa: F401  (collected: a module fixture)
 from test_ppo_net_host import FIELDS, NA, NETS, expand, net_oracle, params_of, quantities, tensors_of, torch_passes
 
@@ -357,24 +355,6 @@ def test_one_minibatch_is_one_linear_graph(collected):
 
 
 # ---------------------------------------------------------------------------------------------------
-def run_nets_update(agent, store, device_adam, target_kl):
-    import torch
-    from splendor_gym.ppo import DeviceAdam, ppo_update
-    a = copy.deepcopy(agent)
-    make = DeviceAdam if device_adam else torch.optim.Adam
-    opt = make(list(a.parameters()), lr=LR, eps=EPS)
-    gen = torch.Generator(device=DEV).manual_seed(0)
-    res = ppo_update(a, opt, store, update_epochs=2, minibatch_size=64, target_kl=target_kl, generator=gen, device_nets=True)
-    return list(a.parameters()), res, opt
-
-
-@pytest.fixture(scope="module")
-def reference_update(collected):
-    """The float64 update without a gate, shared by the tests below (nothing changes it)."""
-    agent, store = collected
-    return update_f64(agent, store, 2, 64, 0.0)
-
-
 def test_ppo_update_with_device_nets(collected, reference_update):
     agent, store = collected
     want, kls, steps = reference_update
@@ -384,7 +364,7 @@ def test_ppo_update_with_device_nets(collected, reference_update):
     p_ref_dev, res_ref_dev, _ = run_update(agent, store, True, 0.0)  # the existing fused path, DeviceAdam
     for device_adam, existing in ((True, res_ref_dev), (False, res_ref)):
         label = f"ppo_update(device_nets) {'DeviceAdam' if device_adam else 'torch.optim.Adam'}"
-        p, res, opt = run_nets_update(agent, store, device_adam, 0.0)
+        p, res, opt = run_update(agent, store, device_adam, 0.0, device_nets=True)
         assert res["optimizer_steps"] == existing["optimizer_steps"] == 8
         assert set(res) == set(existing)
         compare(label, p, p_ref, want, 8)
@@ -397,24 +377,12 @@ def test_ppo_update_with_device_nets(collected, reference_update):
 
 
 def test_ppo_update_with_device_nets_stops_where_the_float64_loop_stops(collected, reference_update):
-    """target_kl between two of the run's minibatch KLs, chosen as test_gpu_ppo_adam.py chooses it: of the
-    midpoints from which every KL of the gated float64 run stays well away, the one that stops it earliest."""
+    """target_kl between two of the run's minibatch KLs, chosen as test_gpu_ppo_adam.py chooses it."""
     agent, store = collected
     _, kls, _ = reference_update
-    e32 = abs(run_update(agent, store, False, 0.0)[1]["approx_kl"] - kls[-1])
-    s, best = sorted(kls), None
-    for a, b in zip(s, s[1:]):
-        if a + b > 0:
-            target = (a + b) / 2
-            _, ran, n = update_f64(agent, store, 2, 64, target)
-            margin = min(abs(k - target) for k in ran)
-            print(f"target {target:.3e}: the float64 loop takes {n} steps, nearest KL {margin:.3e} away")
-            if margin > 100 * e32 and margin > 1e-3 * target and (best is None or n < best[0]):
-                best = (n, target)
-    assert best is not None and best[0] < 8  # the gate acts
-    want_steps, target = best
-    _, res_dev, opt = run_nets_update(agent, store, True, target)
-    _, res_opt, _ = run_nets_update(agent, store, False, target)
+    want_steps, target, _ = choose_target_kl(agent, store, kls)
+    _, res_dev, opt = run_update(agent, store, True, target, device_nets=True)
+    _, res_opt, _ = run_update(agent, store, False, target, device_nets=True)
     assert res_dev["optimizer_steps"] == res_opt["optimizer_steps"] == want_steps
     assert res_dev["gated"] == 8 - want_steps and opt.target_kl == target
 
@@ -429,20 +397,5 @@ def test_ppo_update_refuses_nets_of_another_agent(collected):
 
 
 def test_cli_device_nets():
-    """python -m splendor_gym.scripts.ppo_device --device-nets at the smallest shape in a child process: one
-    update, exit 0, every printed figure finite."""
-    import re
-    here = os.path.dirname(os.path.abspath(__file__))
-    pkg = os.path.join(os.path.dirname(here), "splendor-gym_amd")
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([pkg] + [x for x in (os.environ.get("PYTHONPATH"),) if x]))
-    r = subprocess.run([sys.executable, "-m", "splendor_gym.scripts.ppo_device", "--num-envs", "64", "--num-steps", "4",
-                        "--total-timesteps", str(64 * 4), "--minibatch-size", "128", "--update-epochs", "1", "--pool-size", "2",
-                        "--device-nets", "--device-adam", "--load-path",
-                        os.path.join(here, "golden", "ppo_splendor_latest.safetensors")],
-                       env=env, capture_output=True, text=True, timeout=240)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("update ")]
-    assert len(lines) == 1 and lines[0].startswith("update 1/1 steps 256 "), r.stdout[-2000:]
-    nums = re.findall(r"(?:pl|vl|ent|kl) ([-+0-9.einfa]+)", lines[0])
-    assert len(nums) == 4 and all(np.isfinite(float(x)) for x in nums), lines[0]
-    assert 1 <= int(re.search(r"opt-steps (\d+)", lines[0]).group(1)) <= 2, lines[0]
+    """ppo_device --device-nets at the smallest shape: one update, every printed figure finite."""
+    finite_figures(run_cli("--update-epochs", "1", "--device-nets", "--device-adam", updates=1)[0], 2)

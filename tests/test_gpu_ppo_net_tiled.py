@@ -4,15 +4,12 @@ holds against the float64 oracle.  The f32-input matrix instruction is a k-order
 and so are the existing kernels, so every comparison here is on int32 views and none has a tolerance: a
 difference is a bug in the tile's summation order, padding or epilogue."""
 import copy
-import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from test_gpu_ppo_adam import EPS, LR, bits
+from test_gpu_ppo_adam import EPS, LR, bits, run_cli, run_update
 from test_gpu_ppo_loss import DEV, collected  # noqa: F401  (collected: a module fixture)
 from test_gpu_ppo_net import (COEF, CRAFTED, P, SENTINEL, agents, gaps_untouched, gradients, in_arena, make_idx,  # noqa: F401
                               minibatch, store)
@@ -229,24 +226,12 @@ def test_one_tiled_minibatch_is_one_linear_graph(collected):
     assert not torch.equal(bits(a_g.parameters())[0], bits(agent.parameters())[0])  # and the steps were taken
 
 
-def run_nets_update(agent, store, device_adam, tiled):
-    import torch
-    from splendor_gym.ppo import DeviceAdam, DeviceNets, ppo_update
-    a = copy.deepcopy(agent)
-    make = DeviceAdam if device_adam else torch.optim.Adam
-    opt = make(list(a.parameters()), lr=LR, eps=EPS)
-    gen = torch.Generator(device=DEV).manual_seed(0)
-    res = ppo_update(a, opt, store, update_epochs=2, minibatch_size=64, target_kl=0.0, generator=gen,
-                     device_nets=DeviceNets(a, tiled=tiled))
-    return bits(a.parameters()), res
-
-
 @pytest.mark.parametrize("device_adam", [True, False])
 def test_ppo_update_with_tiled_nets(collected, device_adam):
     import torch
     agent, store = collected
-    p_ref, res_ref = run_nets_update(agent, store, device_adam, False)
-    p, res = run_nets_update(agent, store, device_adam, True)
+    (p_ref, res_ref, _), (p, res, _) = (run_update(agent, store, device_adam, 0.0, tiled=tiled) for tiled in (False, True))
+    p_ref, p = bits(p_ref), bits(p)
     assert res_ref["optimizer_steps"] == 8 and set(res) == set(res_ref)
     assert all(torch.equal(x, y) for x, y in zip(p, p_ref))
     assert not torch.equal(p[0], bits(agent.parameters())[0])
@@ -291,18 +276,7 @@ def test_auto_switches_at_tiled_min_rows(store, agents):
 def test_cli_tiled_nets():
     """python -m splendor_gym.scripts.ppo_device --device-adam --tiled-nets on at the smallest shape prints the
     update lines of the same run with --device-nets, apart from sps."""
-    here = os.path.dirname(os.path.abspath(__file__))
-    pkg = os.path.join(os.path.dirname(here), "splendor-gym_amd")
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([pkg] + [x for x in (os.environ.get("PYTHONPATH"),) if x]))
-    lines = {}
-    for switch in (("--device-nets",), ("--tiled-nets", "on")):
-        r = subprocess.run([sys.executable, "-m", "splendor_gym.scripts.ppo_device", "--num-envs", "64", "--num-steps", "4",
-                            "--total-timesteps", str(2 * 64 * 4), "--minibatch-size", "128", "--update-epochs", "1",
-                            "--pool-size", "2", "--device-adam", *switch, "--load-path",
-                            os.path.join(here, "golden", "ppo_splendor_latest.safetensors")],
-                           env=env, capture_output=True, text=True, timeout=240)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-        lines[switch] = [re.sub(r" sps \d+", "", ln) for ln in r.stdout.splitlines() if ln.startswith("update ")]
-    first, second = lines.values()
-    assert len(first) == 2 and first[1].startswith("update 2/2 steps 512 ") and " sps " not in first[0], first
+    first, second = ([re.sub(r" sps \d+", "", ln) for ln in run_cli("--update-epochs", "1", "--device-adam", *switch, updates=2)]
+                     for switch in (("--device-nets",), ("--tiled-nets", "on")))
+    assert " sps " not in first[0], first
     assert first == second

@@ -5,6 +5,7 @@ and against the reference's own expression."""
 import ctypes
 
 import numpy as np
+import pytest
 
 
 def gae_oracle(reward, value, done, last_value, gamma, lam):
@@ -153,3 +154,105 @@ def test_gather_refusals():
     for off in (1, 2, 3):
         _refused(lib, lib.spl_ppo_gather(4, gat(**{**full, "obs_u8": P + off}), None), "aligned")
     _refused(lib, lib.spl_ppo_gather(4, gat(**{**full, "idx": P + 4}), None), "aligned")
+
+
+# --------------------------------------------------------------------------------------------
+class StubStore:
+    """What ppo_update's torch head with a torch.optim optimiser needs of a store, on the CPU: .torch, .minibatches
+    and .gather over K x T planes drawn from a seeded generator (the recorded action is always legal; the recorded
+    log-probability is that of a uniform choice among the legal moves, jittered)."""
+    K, T = 2, 16
+
+    def __init__(self, seed):
+        import torch
+        from splendor_gym.ppo import NUM_ACTIONS, OBS_DIM
+        self.torch = torch
+        rng, n = np.random.default_rng(seed), self.K * self.T
+        action = rng.integers(0, NUM_ACTIONS, size=n)
+        mask = (rng.random((n, NUM_ACTIONS)) < 0.5).astype(np.float32)
+        mask[np.arange(n), action] = 1.0
+        logprob = -np.log(mask.sum(axis=1)) + 0.05 * rng.normal(size=n)
+        planes = {"obs": rng.integers(0, 5, size=(n, OBS_DIM)).astype(np.float32), "mask": mask, "action": action.astype(np.int64),
+                  "logprob": logprob.astype(np.float32), "value": rng.normal(size=n).astype(np.float32),
+                  "adv": rng.normal(size=n).astype(np.float32), "ret": rng.normal(size=n).astype(np.float32)}
+        self.planes = {k: torch.from_numpy(v) for k, v in planes.items()}
+
+    def minibatches(self, batch_size, generator=None):
+        perm = self.torch.randperm(self.K * self.T, generator=generator)
+        for start in range(0, self.K * self.T, batch_size):
+            yield perm[start:start + batch_size]
+
+    def gather(self, idx, normalize=True):
+        return {k: v[idx] for k, v in self.planes.items()}
+
+
+def _fresh_agent():
+    import torch
+    from splendor_gym.policy import ActorCritic
+    torch.manual_seed(3)
+    return ActorCritic()
+
+
+def _straight_line_update(store, epochs, minibatch, target_kl):
+    """The loop ppo_update must be, written out: float32, default coefficients, clip_grad_norm_ + torch.optim.Adam,
+    the reference's `break`.  Returns the parameters, (epoch, KL) of every minibatch that ran and the last
+    minibatch's statistics."""
+    import torch
+    a = _fresh_agent()
+    opt = torch.optim.Adam(a.parameters(), lr=2.5e-4, eps=1e-5)
+    gen = torch.Generator().manual_seed(0)
+    ran, last = [], None
+    for epoch in range(epochs):
+        for idx in store.minibatches(minibatch, gen):
+            mb = store.gather(idx)
+            _, new_logprob, entropy, new_value = a.get_action_and_value(mb["obs"], mb["mask"], mb["action"])
+            ratio = (new_logprob - mb["logprob"]).exp()
+            clip_adv = torch.clamp(ratio, 1 - 0.2, 1 + 0.2) * mb["adv"]
+            policy_loss = -torch.min(ratio * mb["adv"], clip_adv).mean()
+            v_pred = new_value.squeeze(-1)
+            v_clipped = mb["value"] + torch.clamp(v_pred - mb["value"], -0.2, 0.2)
+            value_loss = 0.5 * torch.max((v_pred - mb["ret"]).pow(2), (v_clipped - mb["ret"]).pow(2)).mean()
+            loss = policy_loss + 0.5 * value_loss + 0.03 * entropy.mean()
+            opt.zero_grad()
+            loss.backward()
+            torch.nn.utils.clip_grad_norm_(a.parameters(), 0.5)
+            opt.step()
+            kl = float((mb["logprob"] - new_logprob).mean().detach())
+            ran.append((epoch, kl))
+            last = {"policy_loss": float(policy_loss.detach()), "value_loss": float(value_loss.detach()),
+                    "entropy": float(entropy.mean().detach()), "approx_kl": kl}
+            if target_kl > 0 and kl > target_kl:
+                break
+    return list(a.parameters()), ran, last
+
+
+def test_ppo_update_is_the_straight_line_loop():
+    """ppo_update's torch head with torch.optim.Adam on a CPU stub store against the loop written out above, bit for
+    bit: without a gate, and with a target between two neighbouring KLs of the ungated run that the first epoch
+    crosses before its last minibatch.  The `break` ends that epoch only: the second one still runs."""
+    import torch
+    from splendor_gym.ppo import ppo_update
+    store = StubStore(5)
+    _, ungated, _ = _straight_line_update(store, 2, 8, 0.0)
+    assert [e for e, _ in ungated] == [0] * 4 + [1] * 4
+    early = sorted(kl for _, kl in ungated[:3])
+    target = (early[-2] + early[-1]) / 2  # the largest of the first three minibatches' KLs crosses it, the others do not
+    assert target > 0 and early[-2] < target < early[-1]
+    for target_kl in (0.0, target):
+        want, ran, last = _straight_line_update(store, 2, 8, target_kl)
+        agent = _fresh_agent()
+        opt = torch.optim.Adam(agent.parameters(), lr=2.5e-4, eps=1e-5)
+        res = ppo_update(agent, opt, store, update_epochs=2, minibatch_size=8, target_kl=target_kl,
+                         generator=torch.Generator().manual_seed(0))
+        assert set(res) == {"policy_loss", "value_loss", "entropy", "approx_kl", "first_approx_kl", "optimizer_steps"}
+        assert res["optimizer_steps"] == len(ran) and res["first_approx_kl"] == ran[0][1]
+        assert {k: res[k] for k in last} == last
+        assert all(torch.equal(p.detach(), w.detach()) for p, w in zip(agent.parameters(), want))
+        first, second = ([kl for e, kl in ran if e == epoch] for epoch in (0, 1))
+        if target_kl:
+            assert len(first) < 4 and first[-1] > target_kl and all(kl <= target_kl for kl in first[:-1])
+            assert len(second) >= 1  # the break ended the first epoch, not the update
+        else:
+            assert len(first) == len(second) == 4
+    with pytest.raises(ValueError, match="update_epochs must be at least 1"):
+        ppo_update(agent, opt, store, update_epochs=0)
