@@ -14,11 +14,13 @@
  *                            itself), the six plane products of order <= 2 accumulated in fp32 on
  *                            v_mfma_f32_16x16x32_bf16 (the dropped terms are <= 2^-24 of each
  *                            product); the observation exact (one plane below 256, a residual plane
- *                            where a value is larger, < 2^16); fp32 tanh to a few ulp
+ *                            where a value is larger, < 2^16); fp32 tanh to a few ulp (0.73 measured
+ *                            over chosen arguments, 4 tested)
  *                            (spl_policy32.hip, k_act32)
  *   SPL_PREC_FP32_F16X2      fp32 within 2^-22: two fp16 planes per operand (22 significant bits,
  *                            weights scaled per row by a power of two), three plane products on
- *                            v_mfma_f32_16x16x32_f16, tanh with ~1e-7 absolute error (k_act32h): the
+ *                            v_mfma_f32_16x16x32_f16, tanh with 1.0e-7 absolute error and, from a cubic
+ *                            below 2^-4, at most 4.4e-6 relative error (k_act32h, spl_policy32.hip): the
  *                            round-4 form, faster, not an exact operand representation
  *   SPL_PREC_BF16 (opt-in)   bf16 MFMA (v_mfma_f32_32x32x16_bf16) with fp32 accumulation (spl_policy.hip)
  *
