@@ -364,6 +364,40 @@ int spl_ppo_net_backward(int32_t B, const spl_ppo_net_bwd_t *args, void *stream)
 int spl_ppo_net_forward_tiled(int32_t B, const spl_ppo_net_fwd_t *args, void *stream);
 int spl_ppo_net_backward_tiled(int32_t B, const spl_ppo_net_bwd_t *args, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * spl_ppo_net_forward_bf16 / spl_ppo_net_backward_bf16: the tiled passes with bf16 operands on the bf16
+ * matrix instruction, float32 accumulation, float32 master weights (SPL_PPO_NET_BF16 advertises them;
+ * SPL_PPO_ABI is unchanged, nothing above moved).  Opt-in: the numbers DIFFER from the two pairs above, so
+ * a training run that switches them on is another run.
+ *
+ * Same argument blocks, same spl_ppo_net_act_bytes / spl_ppo_net_scratch_bytes, same refusals before any
+ * launch, same float32 buffer layouts (`act` [network][layer][B][256], the head of `scratch`
+ * [network][dZ2, dZ1][B][256], then the partials), same treatment of a bad row, same launches as the tiled
+ * pair (forward three, backward four), asynchronous on `stream`, nothing allocated, no floating-point
+ * atomics.  The sums over rows are split by SPL_PPO_NET_BWD_ROWS / SPL_PPO_NET_BWD_PARTS, never by the
+ * device: two calls on the same bytes give the same bytes.  The twelve gradients are overwritten.
+ *
+ * The arithmetic:
+ *   - Matrix-instruction products.  Every product issued on the matrix instruction takes BOTH operands
+ *     rounded from float32 to bf16, round-to-nearest-even, as they are staged: the weights W1, W2, W3
+ *     (actor) and their transposed uses in dZ2 / dZ1; the hidden activations H1, H2; dlogits, dvalue, dZ2
+ *     and dZ1 in the sums over rows.  A bf16 x bf16 product is exact in float32; the sum is accumulated in
+ *     float32 by the instruction, from the bias in the forward layers and from zero elsewhere.  The order
+ *     inside an instruction is the hardware's and no part of this contract.
+ *   - The inputs X enter exactly.  Every column is a byte (exact in bf16) except column 295 = byte 295 +
+ *     256 * byte 297, which is fed as two k-positions, byte 295 at k = 295 and 256 * byte 297 at the pad
+ *     position k = 297, both against W1[:, 295]; in dW1 the two positions' sums are added into column 295.
+ *     No input value is ever rounded.
+ *   - Everything elementwise stays float32: the bias add (the accumulator's start), tanh (4 ulp), fma(-h, h,
+ *     1), the zeros of a bad row, the saved activations and dZ planes as stored.
+ *   - VALU products take unrounded float32 operands: the critic's single output unit, the critic's
+ *     elementwise dZ2, and the bias gradients (plain float32 sums down the rows).
+ *   - Master weights, moments and spl_ppo_adam stay float32; nothing outside these two calls changes.
+ *   - Denormal operands: whether the bf16 instruction flushes them is unspecified. */
+#define SPL_PPO_NET_BF16 1
+int spl_ppo_net_forward_bf16(int32_t B, const spl_ppo_net_fwd_t *args, void *stream);
+int spl_ppo_net_backward_bf16(int32_t B, const spl_ppo_net_bwd_t *args, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,8 @@
-// spl_ppo_net_common.h — what the two sources of the PPO network passes share (spl_ppo_net.hip, the
-// 8-rows-a-workgroup VALU kernels; spl_ppo_net_tiled.hip, the LDS-tiled f32-MFMA kernels): the sizes, the
-// layout of the partial sums in `scratch`, tanh_acc, the kernels' argument blocks and the host-side checks
-// that fill them.  Both sources give the same bytes, so everything that fixes a summation order is here.
+// spl_ppo_net_common.h — what the sources of the PPO network passes share (spl_ppo_net.hip, the
+// 8-rows-a-workgroup VALU kernels; spl_ppo_net_tiled.hip, the LDS-tiled f32-MFMA kernels; spl_ppo_net_bf16.hip,
+// the same tiles with bf16 operands): the sizes, the layout of the partial sums in `scratch`, tanh_acc, the
+// kernels' argument blocks and the host-side checks that fill them.  The two f32 sources give the same bytes,
+// so everything that fixes a summation order is here; the bf16 source keeps the split of the sums over rows.
 #pragma once
 #include "../../include/splendor_ppo.h"
 #include "spl_common.h"

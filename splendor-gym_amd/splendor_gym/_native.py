@@ -141,6 +141,7 @@ class PpoAdam(ctypes.Structure):
 PPO_NET_MAX_ROWS, PPO_NET_HIDDEN = 65536, 256                     # SPL_PPO_NET_*
 PPO_NET_FWD_ROWS, PPO_NET_BWD_ROWS, PPO_NET_BWD_PARTS = 8, 128, 32  # rows per forward tile, per backward partial's chunk
 PPO_NET_TILED, PPO_NET_TILE_ROWS = 1, 64  # SPL_PPO_NET_TILED; rows per workgroup of the tiled forward and dZ launches
+PPO_NET_BF16 = 1                          # SPL_PPO_NET_BF16: the tiled passes with bf16 operands on the matrix cores
 
 
 class PpoMlp(ctypes.Structure):
@@ -271,6 +272,8 @@ SIGNATURES = {
     "spl_ppo_net_backward": ([c_int32, ctypes.POINTER(PpoNetBwd), c_void_p], c_int32),
     "spl_ppo_net_forward_tiled": ([c_int32, ctypes.POINTER(PpoNetFwd), c_void_p], c_int32),
     "spl_ppo_net_backward_tiled": ([c_int32, ctypes.POINTER(PpoNetBwd), c_void_p], c_int32),
+    "spl_ppo_net_forward_bf16": ([c_int32, ctypes.POINTER(PpoNetFwd), c_void_p], c_int32),
+    "spl_ppo_net_backward_bf16": ([c_int32, ctypes.POINTER(PpoNetBwd), c_void_p], c_int32),
     # include/splendor_eval.h
     "spl_eval_abi_version": ([], c_int32),
     "spl_eval_scripted_act": ([c_int32, ctypes.POINTER(EvalAct), c_void_p], c_int32),
@@ -280,8 +283,9 @@ SIGNATURES = {
 }
 
 # what a library built from an earlier header may lack (SPLENDOR_AMD_LIB can name one): it still loads, and
-# what needs these asks has_net_tiled() first
+# what needs these asks has_net_tiled() / has_net_bf16() first
 OPTIONAL = ("spl_ppo_net_forward_tiled", "spl_ppo_net_backward_tiled")
+OPTIONAL_BF16 = ("spl_ppo_net_forward_bf16", "spl_ppo_net_backward_bf16")
 
 
 class NativeError(RuntimeError):
@@ -310,7 +314,7 @@ def load_library():
                           "`python -c 'import __graft_entry__ as g; g.build()'` (no CPU fallback exists)")
     lib = ctypes.CDLL(path)
     for name, (argtypes, restype) in SIGNATURES.items():
-        if name in OPTIONAL and not hasattr(lib, name):
+        if name in OPTIONAL + OPTIONAL_BF16 and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
         fn.argtypes = argtypes
@@ -324,6 +328,11 @@ def load_library():
 def has_net_tiled(lib):
     """the library exports spl_ppo_net_forward_tiled / spl_ppo_net_backward_tiled (SPL_PPO_NET_TILED)"""
     return all(hasattr(lib, name) for name in OPTIONAL)
+
+
+def has_net_bf16(lib):
+    """the library exports spl_ppo_net_forward_bf16 / spl_ppo_net_backward_bf16 (SPL_PPO_NET_BF16)"""
+    return all(hasattr(lib, name) for name in OPTIONAL_BF16)
 
 
 def check(lib, code):

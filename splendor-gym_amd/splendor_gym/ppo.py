@@ -25,6 +25,8 @@ The head is torch autograd (the default), ``PPORolloutStore.loss`` behind the tw
     gradients where the optimiser reads them.  ``DeviceNets(agent, tiled=True | "auto")`` runs the passes on
     the LDS-tiled matrix-core kernels built for minibatches of thousands of rows
     (spl_ppo_net_forward_tiled / spl_ppo_net_backward_tiled), with the same bytes;
+    ``DeviceNets(agent, operands="bf16")`` is the opt-in mixed precision: bf16 operands on the matrix cores,
+    float32 accumulation and master weights (spl_ppo_net_forward_bf16 / spl_ppo_net_backward_bf16), other numbers;
   * ``DeviceAdam``  what follows the head as one device call per minibatch (spl_ppo_adam): the global-norm
     clip, torch.optim.Adam's step and the target-KL early stop, decided on the device, so that
     ``ppo_update`` with it reads the device once per update instead of once per minibatch.
@@ -556,15 +558,24 @@ class DeviceNets(_OnDevice):
     (the default) the 8-rows-a-workgroup passes built for minibatches of a few hundred rows, True the
     LDS-tiled matrix-core passes (spl_ppo_net_forward_tiled / spl_ppo_net_backward_tiled) built for tens of
     thousands, "auto" the tiled ones from TILED_MIN_ROWS rows upward.  A library without the tiled calls is
-    a RuntimeError for anything but False."""
+    a RuntimeError for anything but False.
+
+    `operands` chooses the number format of the matrix products: "f32" (the default) the two pairs above,
+    "bf16" the opt-in mixed-precision pair (spl_ppo_net_forward_bf16 / spl_ppo_net_backward_bf16): both
+    operands of every matrix-core product rounded to bf16, float32 accumulation, float32 master weights and
+    everything elementwise in float32, the inputs exact.  It is used at every B and `tiled` is then not
+    consulted, so a run's numbers do not depend on the minibatch size; they do differ from an "f32" run's.
+    A library without SPL_PPO_NET_BF16 is a RuntimeError."""
     MAX_ROWS = _native.PPO_NET_MAX_ROWS
     TILE_ROWS = _native.PPO_NET_TILE_ROWS
     TILED_MIN_ROWS = 4096  # the smallest benchmarked B at which the tiled passes beat the others (profiles/ppo/bench_ppo_nets_tiled.json)
 
-    def __init__(self, agent, tiled=False):
+    def __init__(self, agent, tiled=False, operands="f32"):
         import torch
         if not any(tiled is v for v in (False, True)) and tiled != "auto":
             raise ValueError(f"tiled must be False, True or 'auto', not {tiled!r}")
+        if not isinstance(operands, str) or operands not in ("f32", "bf16"):
+            raise ValueError(f"operands must be 'f32' or 'bf16', not {operands!r}")
         nets = []
         for name, n3 in (("actor", NUM_ACTIONS), ("critic", 1)):
             net = getattr(agent, name, None)
@@ -591,9 +602,18 @@ class DeviceNets(_OnDevice):
         if tiled is not False and not _native.has_net_tiled(self.lib):
             raise RuntimeError(f"DeviceNets(tiled={tiled!r}) needs spl_ppo_net_forward_tiled / spl_ppo_net_backward_tiled "
                                f"(SPL_PPO_NET_TILED), which {_native.lib_path()} does not export; rebuild the library")
+        self.operands = operands
+        if operands == "bf16" and not _native.has_net_bf16(self.lib):
+            raise RuntimeError("DeviceNets(operands='bf16') needs spl_ppo_net_forward_bf16 / spl_ppo_net_backward_bf16 "
+                               f"(SPL_PPO_NET_BF16), which {_native.lib_path()} does not export; rebuild the library")
 
     def _use_tiled(self, B):
         return self.tiled is True or (self.tiled == "auto" and B >= self.TILED_MIN_ROWS)
+
+    def _call(self, which, B):
+        """spl_ppo_net_<which> of the pair that takes B rows"""
+        suffix = "_bf16" if self.operands == "bf16" else "_tiled" if self._use_tiled(B) else ""
+        return getattr(self.lib, f"spl_ppo_net_{which}{suffix}")
 
     def _mlp(self, tensors):
         return _native.PpoMlp(*(x.data_ptr() for x in tensors))
@@ -628,8 +648,7 @@ class DeviceNets(_OnDevice):
                               critic=self._mlp(self.params[6:]), logits=bufs["logits"].data_ptr(),
                               new_value=bufs["value"].data_ptr(), act=bufs["act"].data_ptr(), errors=store.errors.data_ptr())
         with self.torch.cuda.device(self.device):
-            call = self.lib.spl_ppo_net_forward_tiled if self._use_tiled(B) else self.lib.spl_ppo_net_forward
-            check(self.lib, call(B, ctypes.byref(a), self._stream()))
+            check(self.lib, self._call("forward", B)(B, ctypes.byref(a), self._stream()))
         bufs["idx"] = idx
         return bufs["logits"], bufs["value"]
 
@@ -657,8 +676,7 @@ class DeviceNets(_OnDevice):
                               act=bufs["act"].data_ptr(), actor_grad=self._mlp(grads[:6]), critic_grad=self._mlp(grads[6:]),
                               scratch=bufs["scratch"].data_ptr())
         with t.cuda.device(self.device):
-            call = self.lib.spl_ppo_net_backward_tiled if self._use_tiled(B) else self.lib.spl_ppo_net_backward
-            check(self.lib, call(B, ctypes.byref(a), self._stream()))
+            check(self.lib, self._call("backward", B)(B, ctypes.byref(a), self._stream()))
         bufs["idx"] = idx
 
 

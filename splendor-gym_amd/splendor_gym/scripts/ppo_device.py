@@ -10,7 +10,9 @@ as one device call; --device-adam: the norm clip, the Adam step and the target-K
 per minibatch, so that an update reads the device once; --device-nets: the two networks' forward and
 backward passes as device calls too, a minibatch then being four device calls; --tiled-nets on | auto: those
 passes by the LDS-tiled matrix-core kernels built for minibatches of tens of thousands of rows, always or
-from DeviceNets.TILED_MIN_ROWS rows upward, with the same bytes either way).  After each update the
+from DeviceNets.TILED_MIN_ROWS rows upward, with the same bytes either way; --net-operands bf16: those
+passes with bf16 operands on the matrix cores at every minibatch size, float32 accumulation and master
+weights, which is another run: its numbers differ).  After each update the
 fused agent and the pool re-pack the new weights; every --snapshot-every-updates updates the pool takes
 a snapshot.  --eval-every-updates N evaluates before training and every N updates, --eval-games games
 against each of random, greedy_v1, basic, the agent itself and greedy_v2 in one batch on the device
@@ -58,12 +60,15 @@ def main(argv=None):
     p.add_argument("--tiled-nets", choices=("off", "auto", "on"), default="off",
                    help="DeviceNets' passes on the tiled matrix-core kernels: on always, auto from DeviceNets.TILED_MIN_ROWS "
                         "rows a minibatch upward; the same bytes as off; auto and on imply --device-nets")
+    p.add_argument("--net-operands", choices=("f32", "bf16"), default="f32",
+                   help="DeviceNets' matrix products: f32, or bf16 operands with float32 accumulation and float32 master "
+                        "weights (mixed precision: the numbers of the run change); bf16 implies --device-nets")
     p.add_argument("--no-graph", action="store_true", help="run every rollout eagerly instead of replaying a hipGraph")
     p.add_argument("--eval-every-updates", type=int, default=0,
                    help="evaluate before training and every N updates (0: never), as ppo_splendor.py does")
     p.add_argument("--eval-games", type=int, default=400, help="games per opponent kind of one evaluation")
     args = p.parse_args(argv)
-    args.device_nets = args.device_nets or args.tiled_nets != "off"
+    args.device_nets = args.device_nets or args.tiled_nets != "off" or args.net_operands != "f32"
 
     import torch
     from ..fused_policy import FusedActorCritic, OpponentPool
@@ -84,7 +89,8 @@ def main(argv=None):
         optimizer = DeviceAdam(agent.parameters(), lr=args.lr, eps=1e-5, target_kl=args.target_kl)
     else:
         optimizer = torch.optim.Adam(agent.parameters(), lr=args.lr, eps=1e-5)
-    nets = DeviceNets(agent, tiled={"off": False, "auto": "auto", "on": True}[args.tiled_nets]) if args.device_nets else False
+    nets = DeviceNets(agent, tiled={"off": False, "auto": "auto", "on": True}[args.tiled_nets],
+                      operands=args.net_operands) if args.device_nets else False
     agent_k = FusedActorCritic(agent)
     pool =OpponentPool(agent, pool_size=args.pool_size, p_current=args.p_current, seed=args.seed)
     counter = torch.zeros(1, dtype=torch.int64, device=dev)

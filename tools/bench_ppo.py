@@ -20,10 +20,12 @@ medians reported:
      the host clock, at the reference's shape (128 steps x 16 tables, minibatch 256, 4 epochs) and at 128 x
      4 096 with minibatch 65 536.  It builds its own small stores; --adam-only runs nothing else.
   6. nets (--nets-only, not part of the default run): DeviceNets.forward + backward (spl_ppo_net_forward /
-     spl_ppo_net_backward) and DeviceNets(tiled=True) (spl_ppo_net_forward_tiled / spl_ppo_net_backward_tiled)
+     spl_ppo_net_backward), DeviceNets(tiled=True) (spl_ppo_net_forward_tiled / spl_ppo_net_backward_tiled)
+     and DeviceNets(operands="bf16") (spl_ppo_net_forward_bf16 / spl_ppo_net_backward_bf16, other numbers)
      beside store.gather + the two torch networks + torch.autograd.backward for fixed dlogits / dvalue, at
      B = 256, 4 096, 16 384 and 65 536; and one whole ppo_update(fused_loss=True, target_kl=0.02) with
-     DeviceAdam without device_nets, with them and with the tiled ones, at the same two shapes as in 5.
+     DeviceAdam without device_nets, with them, with the tiled ones and with the bf16 ones, at the same two
+     shapes as in 5 (--nets-json profiles/ppo/bench_ppo_nets_bf16.json keeps the section).
 Bytes are the algorithmic bytes each kernel has to move, computed from the shapes below.
 """
 import argparse
@@ -45,7 +47,7 @@ def main():
     ap.add_argument("--loss-json", default="", help="also write the loss section to this file (profiles/ppo/bench_ppo_loss.json)")
     ap.add_argument("--adam-json", default="", help="also write the optimiser section to this file (profiles/ppo/bench_ppo_adam.json)")
     ap.add_argument("--adam-only", action="store_true", help="run the optimiser section alone")
-    ap.add_argument("--nets-json", default="", help="also write the network section to this file (profiles/ppo/bench_ppo_nets_tiled.json)")
+    ap.add_argument("--nets-json", default="", help="also write the network section to this file (profiles/ppo/bench_ppo_nets_bf16.json)")
     ap.add_argument("--nets-only", action="store_true", help="run the network-pass section alone")
     args = ap.parse_args()
 
@@ -66,9 +68,10 @@ def main():
         m.load_state_dict(load_file(ckpt, device=str(dev)))
         return m
 
-    def timed(arms, inner=1, repeats=args.repeats, before=None):
+    def timed(arms, inner=1, repeats=args.repeats, before=None, spread=None):
         """median milliseconds per call of each arm (`inner` back-to-back calls per timed window), the arms
-        alternating; one untimed call of each first; `before` runs ahead of every timed window"""
+        alternating; one untimed call of each first; `before` runs ahead of every timed window; `spread`, a
+        dictionary, takes each arm's (fastest, slowest) window"""
         for fn in arms.values():
             fn()
         torch.cuda.synchronize(dev)
@@ -84,6 +87,8 @@ def main():
                 b.record()
                 b.synchronize()
                 ms[name].append(a.elapsed_time(b) / inner)
+        if spread is not None:
+            spread.update({name: (min(v), max(v)) for name, v in ms.items()})
         return {name: statistics.median(v) for name, v in ms.items()}
 
     # ---- 5. the optimiser step (defined here, run last; --adam-only runs nothing else) --------------
@@ -233,8 +238,8 @@ def main():
             idx = torch.randperm(big.num_steps * big.num_envs, device=dev, generator=gen)[:B].contiguous()
             dlogits = torch.randn(B, 45, device=dev, generator=gen) / B
             dvalue = torch.randn(B, device=dev, generator=gen) / B
-            a_dev, a_ref, a_tiled = copy.deepcopy(trained), copy.deepcopy(trained), copy.deepcopy(trained)
-            nets, tiled = DeviceNets(a_dev), DeviceNets(a_tiled, tiled=True)
+            a_dev, a_ref, a_tiled, a_bf16 = (copy.deepcopy(trained) for _ in range(4))
+            nets, tiled, bf16 = DeviceNets(a_dev), DeviceNets(a_tiled, tiled=True), DeviceNets(a_bf16, operands="bf16")
             ref_params = list(a_ref.parameters())
 
             def device_arm():
@@ -245,19 +250,30 @@ def main():
                 tiled.forward(big, idx)
                 tiled.backward(big, idx, dlogits, dvalue)
 
+            def bf16_arm():
+                bf16.forward(big, idx)
+                bf16.backward(big, idx, dlogits, dvalue)
+
             def torch_arm():
                 for p in ref_params:
                     p.grad = None
                 obs = big.gather(idx)["obs"]
                 torch.autograd.backward([a_ref.actor(obs), a_ref.critic(obs)], [dlogits, dvalue.view(B, 1)])
 
-            ms = timed({"device": device_arm, "torch": torch_arm, "tiled": tiled_arm}, inner=100)
+            spread = {}
+            ms = timed({"device": device_arm, "torch": torch_arm, "tiled": tiled_arm, "bf16": bf16_arm}, inner=100, spread=spread)
+            rel = lambda xs, ys: float(torch.sqrt(sum(((x.grad - y.grad).double() ** 2).sum() for x, y in zip(xs, ys)) /
+                                                  sum((y.grad.double() ** 2).sum() for y in ys)))
             same = all(torch.equal(p.grad.view(torch.int32), q.grad.view(torch.int32))
                        for p, q in zip(a_dev.parameters(), a_tiled.parameters()))
             diff = max(float((p.grad - q.grad).abs().max()) for p, q in zip(a_dev.parameters(), ref_params))
             scale = max(float(q.grad.abs().max()) for q in ref_params)
             passes[f"B{B}"] = {"device_us": round(ms["device"] * 1e3, 1), "torch_us": round(ms["torch"] * 1e3, 1),
-                               "tiled_us": round(ms["tiled"] * 1e3, 1),
+                               "tiled_us": round(ms["tiled"] * 1e3, 1), "bf16_us": round(ms["bf16"] * 1e3, 1),
+                               "tiled_us_fastest_slowest": [round(x * 1e3, 1) for x in spread["tiled"]],
+                               "bf16_us_fastest_slowest": [round(x * 1e3, 1) for x in spread["bf16"]],
+                               "ratio_tiled_over_bf16": round(ms["tiled"] / ms["bf16"], 2),
+                               "bf16_gradients_relative_l2_to_tiled": rel(list(a_bf16.parameters()), list(a_tiled.parameters())),
                                "ratio_torch_over_device": round(ms["torch"] / ms["device"], 2),
                                "ratio_torch_over_tiled": round(ms["torch"] / ms["tiled"], 2),
                                "ratio_device_over_tiled": round(ms["device"] / ms["tiled"], 2),
@@ -265,7 +281,9 @@ def main():
                                "max_abs_gradient_difference_to_torch": diff, "max_abs_gradient": scale}
         passes["note"] = ("forward and backward of both networks for B store positions, fixed dlogits / dvalue: DeviceNets.forward + "
                           "backward (spl_ppo_net_forward: 1 launch, spl_ppo_net_backward: 3) and the same with tiled=True "
-                          "(spl_ppo_net_forward_tiled: 3 launches, spl_ppo_net_backward_tiled: 4) beside store.gather + actor + critic + "
+                          "(spl_ppo_net_forward_tiled: 3 launches, spl_ppo_net_backward_tiled: 4) "
+                          "and DeviceNets(operands=\"bf16\") (spl_ppo_net_forward_bf16: 3 launches, spl_ppo_net_backward_bf16: 4; "
+                          "bf16 operands on the matrix cores, other numbers) beside store.gather + actor + critic + "
                           "torch.autograd.backward from cleared gradients; device events around 100 back-to-back iterations, arms "
                           "alternating, medians")
 
@@ -274,7 +292,9 @@ def main():
                 def run():
                     a = copy.deepcopy(trained)
                     opt = DeviceAdam(list(a.parameters()), lr=2.5e-4, eps=1e-5)
-                    nets = DeviceNets(a, tiled=device_nets == "tiled") if device_nets else False
+                    nets = False
+                    if device_nets:
+                        nets = DeviceNets(a, tiled=device_nets == "tiled", operands="bf16" if device_nets == "bf16" else "f32")
                     g = torch.Generator(device=dev).manual_seed(0)
                     torch.cuda.synchronize(dev)
                     t0 = time.perf_counter()
@@ -284,7 +304,7 @@ def main():
                     return (time.perf_counter() - t0) * 1e3, res
                 return run
 
-            runs = {"torch_nets": arm(False), "device_nets": arm(True), "tiled_nets": arm("tiled")}
+            runs = {"torch_nets": arm(False), "device_nets": arm(True), "tiled_nets": arm("tiled"), "bf16_nets": arm("bf16")}
             for fn in runs.values():
                 fn()
             times, last = {k: [] for k in runs}, {}
@@ -295,10 +315,12 @@ def main():
             out = {}
             for name in runs:
                 out[f"{name}_ms"] = round(statistics.median(times[name]), 3)
+                out[f"{name}_ms_fastest_slowest"] = [round(min(times[name]), 3), round(max(times[name]), 3)]
                 out[f"{name}_optimizer_steps"] = last[name]["optimizer_steps"]
             total = store.num_steps * store.num_envs
             out.update({"ratio_torch_over_device": round(out["torch_nets_ms"] / out["device_nets_ms"], 3),
                         "ratio_torch_over_tiled": round(out["torch_nets_ms"] / out["tiled_nets_ms"], 3),
+                        "ratio_tiled_over_bf16": round(out["tiled_nets_ms"] / out["bf16_nets_ms"], 3),
                         "faster": min(runs, key=lambda name: out[f"{name}_ms"]),
                         "minibatches_run": 4 * -(-total // minibatch), "K": store.num_steps, "T": store.num_envs,
                         "minibatch": minibatch, "epochs": 4})
@@ -306,12 +328,12 @@ def main():
 
         updates = {"reference_shape": update_arms(collected(16, 128), 256), "large": update_arms(big, 65536)}
         updates["note"] = ("one ppo_update(fused_loss=True, target_kl=0.02) with DeviceAdam from the trained checkpoint, without "
-                           "device_nets, with them and with DeviceNets(tiled=True) (a DeviceNets built outside the clock, as the optimiser is), host clock from the call to "
+                           "device_nets, with them, with DeviceNets(tiled=True) and with DeviceNets(operands=\"bf16\") (a DeviceNets built outside the clock, as the optimiser is), host clock from the call to "
                            "a device synchronise behind it, arms alternating, medians")
         section = {"passes": passes, "ppo_update": updates}
         if args.nets_json:
             with open(args.nets_json, "w") as f:
-                json.dump({"metric": "PPO network passes (spl_ppo_net_forward / spl_ppo_net_backward and their _tiled forms) and whole updates, one MI355X",
+                json.dump({"metric": "PPO network passes (spl_ppo_net_forward / spl_ppo_net_backward, their _tiled and their _bf16 forms) and whole updates, one MI355X",
                            "repeats": args.repeats, "nets": section}, f, indent=1)
                 f.write("\n")
         return section

@@ -16,7 +16,8 @@ for line in sys.stdin:
         cur = {"name": subprocess.run(["c++filt", v], capture_output=True, text=True).stdout.strip()}; rows.append(cur)
     elif cur is not None:
         cur[k] = v
-cols = ["VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "LDS Size [bytes/block]"]
+cols = ["VGPRs", "AGPRs", "TotalSGPRs", "SGPRs Spill", "VGPRs Spill", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]",
+        "LDS Size [bytes/block]"]
 print("kernel | " + " | ".join(c.split(" [")[0] for c in cols))
 for r in rows:
     if "(" in r["name"] and "k_" in r["name"]:
