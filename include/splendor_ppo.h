@@ -398,6 +398,56 @@ int spl_ppo_net_backward_tiled(int32_t B, const spl_ppo_net_bwd_t *args, void *s
 int spl_ppo_net_forward_bf16(int32_t B, const spl_ppo_net_fwd_t *args, void *stream);
 int spl_ppo_net_backward_bf16(int32_t B, const spl_ppo_net_bwd_t *args, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * spl_ppo_permute and spl_ppo_loss_dev: what a whole update captured as ONE graph needs from the device
+ * (SPL_PPO_PERMUTE advertises both; SPL_PPO_ABI is unchanged, nothing above moved).  A replayed graph repeats
+ * its kernel arguments, so whatever changes from update to update has to live in device memory: the epoch's
+ * permutation is drawn from a device state block that the call itself advances, and the loss head reads its
+ * four coefficients from a device block that the host rewrites between replays.
+ *
+ * spl_ppo_permute: a keyed permutation of 0 .. n-1, every element computed on its own (no sort, no
+ * atomics) by a keyed bijection with cycle walking:
+ *   n == 1: {0}.  Otherwise bits = max(2, bit_length(n - 1)), a = bits / 2, b = bits - a, and one PASS is
+ *   eight rounds r = 0..7 on x in [0, 2^bits):
+ *     (wl, wr) = (b, a) when r is even, else (a, b)
+ *     L = x >> wr,  R = x & (2^wr - 1)
+ *     f = the .x word of Philox4x32-10(counter = (R, r, draw_lo, draw_hi), key = (seed_lo, seed_hi))
+ *     x = (R << wl) | ((L ^ f) & (2^wl - 1))
+ *   perm[i]: x = i, one pass, and another pass while x >= n.
+ * A pass is a bijection of [0, 2^bits), so the walk from i < n comes back below n, and since 2^bits < 2n
+ * (n >= 3) it takes fewer than two passes on average.  (seed, draw) select the permutation; the call leaves
+ * draw + 1 behind it, so the next call, or the next replay of a captured call, draws the next one.
+ *
+ * Output: element i goes to out[(i / B) * stride + i % B] with stride = B rounded up to even, so minibatch
+ * m = the first min(B, n - m B) words of row m, and every row starts on a 16-byte boundary whatever B is.
+ * The pad word of a row (B odd) and the last row's words past n are written as -1: a consumer that takes
+ * them for positions counts bad rows.  Exactly ceil(n / B) * stride words are written.
+ *
+ * Two launches: the permutation, whose threads all read *state, then one thread that advances state->draw
+ * behind it; no launch writes a word that its other threads read. */
+#define SPL_PPO_PERMUTE 1
+typedef struct { uint64_t seed, draw; } spl_ppo_perm_state_t;   /* device, 16 bytes, 8-byte aligned */
+typedef struct {
+    int64_t n;                      /* positions: 1 .. 2^31 - 1 (SPL_E_RANGE otherwise)                 */
+    int32_t B;                      /* minibatch size: 1 .. n (SPL_E_RANGE otherwise)                   */
+    int32_t reserved;               /* 0                                                               */
+    spl_ppo_perm_state_t *state;    /* read; draw is advanced by 1 behind the permutation              */
+    int64_t *out;                   /* [ceil(n/B)][stride], stride = B rounded up to even; 16-byte
+                                       aligned                                                         */
+} spl_ppo_permute_t;
+/* SPL_E_RANGE for n or B out of range, SPL_E_ARG for a null or misaligned pointer or reserved != 0;
+ * nothing is launched on an error.  Asynchronous on `stream`, nothing allocated */
+int spl_ppo_permute(const spl_ppo_permute_t *args, void *stream);
+
+/* spl_ppo_loss with {clip_coef, vclip, vf_coef, ent_coef} read on the device from coef[0..3] (device,
+ * 16-byte aligned) instead of from the argument block, whose own four fields are ignored.  Everything else
+ * is spl_ppo_loss (the same kernels, the same fixed-order sums): the same inputs give the same bits as
+ * spl_ppo_loss with those four values as arguments.  The host cannot check device values, so what
+ * spl_ppo_loss refuses is handled per call on the device: with a negative or NaN clip_coef, vclip or
+ * vf_coef, or a NaN ent_coef, EVERY row of the call is a bad row: zero gradients, nothing in the sums,
+ * *errors and out->bad rise by B. */
+int spl_ppo_loss_dev(int32_t B, const spl_ppo_loss_t *args, const float *coef, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@
 
 #include "../../include/splendor_ppo.h"
 #include "spl_common.h"
+#include "spl_rng.h"
 
 #include <float.h>
 
@@ -302,9 +303,26 @@ __device__ __forceinline__ void block_sums(double (&q)[kLossSums], double (*lds)
     }
 }
 
+// kDev: the four coefficients come from device memory (spl_ppo_loss_dev) and are checked here, since the
+// host could not: one that spl_ppo_loss refuses makes every row of the call a bad row.  Otherwise they are
+// the argument block's, which the host has checked.
+struct LossCoef {
+    float clip, vclip, vf, ent;
+    bool valid;
+};
+
+template <bool kDev>
+__device__ __forceinline__ LossCoef loss_coef(const spl_ppo_loss_t &g, const float *__restrict__ coef) {
+    if (!kDev) return LossCoef{g.clip_coef, g.vclip, g.vf_coef, g.ent_coef, true};
+    const float4 c = *reinterpret_cast<const float4 *>(coef);
+    return LossCoef{c.x, c.y, c.z, c.w, c.x >= 0.f && c.y >= 0.f && c.z >= 0.f && c.w == c.w};
+}
+
+template <bool kDev>
 __global__ __launch_bounds__(kBlock) void k_loss(int B, int64_t total, float inv_b, spl_ppo_loss_t g,
-                                                 double *__restrict__ partial) {
+                                                 const float *__restrict__ coef, double *__restrict__ partial) {
     constexpr int kA = spl::kActions;
+    const LossCoef cf = loss_coef<kDev>(g, coef);
     __shared__ float tile[kBlock / 64][64 * kA];
     __shared__ double sums[kBlock / 64][kLossSums];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -346,7 +364,7 @@ __global__ __launch_bounds__(kBlock) void k_loss(int B, int64_t total, float inv
         adv = (float)((double)num / (double)den);
     }
     if (!legal) legal = kAllActions;
-    const bool ok = in && act >= 0 && act < kA && ((legal >> act) & 1);
+    const bool ok = in && cf.valid && act >= 0 && act < kA && ((legal >> act) & 1);
     spl::wave_lds_sync();
 
     float *row = t + lane * kA;
@@ -380,22 +398,22 @@ __global__ __launch_bounds__(kBlock) void k_loss(int B, int64_t total, float inv
             H -= p * l;
             lp = j == act ? l : lp;
         }
-        const float c = g.clip_coef, lo = 1.f - c, hi = 1.f + c;
+        const float c = cf.clip, lo = 1.f - c, hi = 1.f + c;
         const float r = expf(lp - lp_old), rc = fminf(fmaxf(r, lo), hi);
         const float s1 = r * adv, s2 = rc * adv;
         const float g_lp = ((r >= lo && r <= hi) || s1 < s2) ? -(adv * r) * inv_b : 0.f;
-        const float g_ent = g.ent_coef * inv_b;
+        const float g_ent = cf.ent * inv_b;
 #pragma unroll
         for (int j = 0; j < kA; ++j) {
             const float p = row[j];
             row[j] = (g_lp * ((j == act ? 1.f : 0.f) - p) - g_ent * p * (x[j] + H)) + 0.f;  // -0 + 0 = +0
         }
-        const float vclip = g.vclip, dlt = v - v_old;
+        const float vclip = cf.vclip, dlt = v - v_old;
         const float v_c = v_old + fminf(fmaxf(dlt, -vclip), vclip);
         const float e1 = v - ret, e2 = v_c - ret, q1 = e1 * e1, q2 = e2 * e2;
         const float w1 = q1 > q2 ? 1.f : q1 < q2 ? 0.f : 0.5f;
         const float through = (dlt >= -vclip && dlt <= vclip) ? (1.f - w1) * e2 : 0.f;
-        dv = g.vf_coef * inv_b * (w1 * e1 + through);
+        dv = cf.vf * inv_b * (w1 * e1 + through);
         q[0] = -(double)fminf(s1, s2);
         q[1] = (double)(0.5f * fmaxf(q1, q2));
         q[2] = (double)H;
@@ -428,10 +446,13 @@ __global__ __launch_bounds__(kBlock) void k_loss(int B, int64_t total, float inv
 }
 
 // one workgroup: lane j adds partials j, j + 256, ... in that order, then block_sums
+// (coef: the device block of spl_ppo_loss_dev, whose vf_coef and ent_coef then replace the arguments)
 __global__ __launch_bounds__(kBlock) void k_loss_finish(int blocks, int B, float vf_coef, float ent_coef,
+                                                        const float *__restrict__ coef,
                                                         const double *__restrict__ partial,
                                                         spl_ppo_loss_out_t *__restrict__ o) {
     __shared__ double sums[kBlock / 64][kLossSums];
+    if (coef) vf_coef = coef[2], ent_coef = coef[3];
     double q[kLossSums] = {};
     for (int p = threadIdx.x; p < blocks; p += kBlock) {
 #pragma unroll
@@ -633,6 +654,54 @@ __global__ void k_adam_begin(spl_ppo_adam_state_t *st, int update) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// permute
+// ---------------------------------------------------------------------------------------------
+// One thread per output word, pads included, so the -1 words need no launch of their own.  Element i is
+// computed from (seed, draw, i) alone: a pass is eight rounds of an alternating Feistel network over the
+// `wa + wb` bits that hold n - 1, Philox4x32-10 as the round function, and passes are repeated until the
+// value falls below n (cycle walking; a pass is a bijection of [0, 2^bits), so the walk from i < n ends).
+// Nothing here writes *state: k_permute_advance does, one thread, behind this launch.
+struct Perm {
+    uint32_t n, B, stride;
+    int wa, wb;     // a = bits / 2, b = bits - a
+    int64_t slots;  // ceil(n / B) * stride
+    const spl_ppo_perm_state_t *state;
+    int64_t *out;
+};
+
+__device__ __forceinline__ uint32_t permute_pass(uint32_t x, int wa, int wb, uint2 key, uint32_t d_lo, uint32_t d_hi) {
+#pragma unroll
+    for (uint32_t r = 0; r < 8; ++r) {
+        const int wl = (r & 1) ? wa : wb, wr = (r & 1) ? wb : wa;
+        const uint32_t L = x >> wr, R = x & ((1u << wr) - 1u);
+        const uint32_t f = spl::philox4x32(make_uint4(R, r, d_lo, d_hi), key).x;
+        x = (R << wl) | ((L ^ f) & ((1u << wl) - 1u));
+    }
+    return x;
+}
+
+__global__ __launch_bounds__(kBlock) void k_permute(Perm p) {
+    const int64_t slot = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (slot >= p.slots) return;
+    const uint64_t seed = p.state->seed, draw = p.state->draw;
+    const uint32_t row = (uint32_t)(slot / p.stride), col = (uint32_t)(slot - (int64_t)row * p.stride);
+    const uint64_t i = (uint64_t)row * p.B + col;  // below 2^32 + 2^31
+    int64_t v = -1;
+    if (col < p.B && i < p.n) {
+        uint32_t x = (uint32_t)i;
+        if (p.n > 1) {
+            const uint2 key = make_uint2((uint32_t)seed, (uint32_t)(seed >> 32));
+            do x = permute_pass(x, p.wa, p.wb, key, (uint32_t)draw, (uint32_t)(draw >> 32));
+            while (x >= p.n);
+        }
+        v = (int64_t)x;
+    }
+    p.out[slot] = v;
+}
+
+__global__ void k_permute_advance(spl_ppo_perm_state_t *st) { st->draw += 1; }
+
 }  // namespace splp
 
 using namespace splp;
@@ -721,7 +790,8 @@ int64_t spl_ppo_loss_scratch_bytes(int32_t B) {
     return (((int64_t)B + kBlock - 1) / kBlock) * kLossSums * (int64_t)sizeof(double);
 }
 
-int spl_ppo_loss(int32_t B, const spl_ppo_loss_t *a, void *stream) {
+// what spl_ppo_loss and spl_ppo_loss_dev check alike; coef: NULL for the argument block's coefficients
+static int loss_call(int32_t B, const spl_ppo_loss_t *a, const float *coef, bool dev, void *stream) {
     if (B < 1) return spl_fail(SPL_E_ARG, "B must be positive");
     if (!a) return spl_fail(SPL_E_ARG, "null loss arguments");
     if (a->K < 1 || a->T < 1) return spl_fail(SPL_E_ARG, "K and T must be positive");
@@ -735,16 +805,57 @@ int spl_ppo_loss(int32_t B, const spl_ppo_loss_t *a, void *stream) {
         spl_misaligned(a->adv, 4) || spl_misaligned(a->ret, 4) || spl_misaligned(a->logits, 4) ||
         spl_misaligned(a->new_value, 4) || spl_misaligned(a->dlogits, 4) || spl_misaligned(a->dvalue, 4))
         return spl_fail(SPL_E_ARG, "action and the float planes must be 4-byte aligned");
-    if (a->clip_coef != a->clip_coef || a->vclip != a->vclip || a->vf_coef != a->vf_coef || a->ent_coef != a->ent_coef)
-        return spl_fail(SPL_E_ARG, "a coefficient is NaN");
-    if (a->clip_coef < 0.f || a->vclip < 0.f || a->vf_coef < 0.f)
-        return spl_fail(SPL_E_ARG, "clip_coef, vclip and vf_coef must not be negative");
+    if (dev) {
+        if (!coef) return spl_fail(SPL_E_ARG, "null buffer");
+        if (spl_misaligned(coef, 16)) return spl_fail(SPL_E_ARG, "coef must be 16-byte aligned");
+    } else {
+        if (a->clip_coef != a->clip_coef || a->vclip != a->vclip || a->vf_coef != a->vf_coef || a->ent_coef != a->ent_coef)
+            return spl_fail(SPL_E_ARG, "a coefficient is NaN");
+        if (a->clip_coef < 0.f || a->vclip < 0.f || a->vf_coef < 0.f)
+            return spl_fail(SPL_E_ARG, "clip_coef, vclip and vf_coef must not be negative");
+    }
     const int blocks = (int)(((int64_t)B + kBlock - 1) / kBlock);
     const hipStream_t s = (hipStream_t)stream;
     double *partial = static_cast<double *>(a->scratch);
-    hipLaunchKernelGGL(k_loss, dim3(blocks), dim3(kBlock), 0, s, B, (int64_t)a->K * a->T, 1.f / (float)B, *a, partial);
-    hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(kBlock), 0, s, blocks, B, a->vf_coef, a->ent_coef, partial, a->out);
+    const int64_t total = (int64_t)a->K * a->T;
+    if (dev)
+        hipLaunchKernelGGL(k_loss<true>, dim3(blocks), dim3(kBlock), 0, s, B, total, 1.f / (float)B, *a, coef, partial);
+    else
+        hipLaunchKernelGGL(k_loss<false>, dim3(blocks), dim3(kBlock), 0, s, B, total, 1.f / (float)B, *a, coef, partial);
+    hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(kBlock), 0, s, blocks, B, a->vf_coef, a->ent_coef, coef, partial, a->out);
     return spl_launched("k_loss");
+}
+
+int spl_ppo_loss(int32_t B, const spl_ppo_loss_t *a, void *stream) { return loss_call(B, a, nullptr, false, stream); }
+
+int spl_ppo_loss_dev(int32_t B, const spl_ppo_loss_t *a, const float *coef, void *stream) {
+    return loss_call(B, a, coef, true, stream);
+}
+
+int spl_ppo_permute(const spl_ppo_permute_t *a, void *stream) {
+    if (!a) return spl_fail(SPL_E_ARG, "null permute arguments");
+    if (a->reserved != 0) return spl_fail(SPL_E_ARG, "reserved must be 0");
+    if (!a->state || !a->out) return spl_fail(SPL_E_ARG, "null buffer");
+    if (spl_misaligned(a->state, 8)) return spl_fail(SPL_E_ARG, "state must be 8-byte aligned");
+    if (spl_misaligned(a->out, 16)) return spl_fail(SPL_E_ARG, "out must be 16-byte aligned");
+    if (a->n < 1 || a->n > (int64_t)INT32_MAX) return spl_fail(SPL_E_RANGE, "n must be in 1 .. 2^31 - 1");
+    if (a->B < 1 || (int64_t)a->B > a->n) return spl_fail(SPL_E_RANGE, "B must be in 1 .. n");
+    Perm p{};
+    p.n = (uint32_t)a->n;
+    p.B = (uint32_t)a->B;
+    p.stride = (p.B + 1u) & ~1u;
+    p.slots = ((a->n + a->B - 1) / a->B) * (int64_t)p.stride;  // at most 2^32: B = 1, stride 2
+    int bits = 0;
+    while (bits < 32 && ((uint64_t)1 << bits) < (uint64_t)a->n) ++bits;  // bit_length(n - 1)
+    if (bits < 2) bits = 2;
+    p.wa = bits / 2;
+    p.wb = bits - p.wa;
+    p.state = a->state;
+    p.out = a->out;
+    const hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_permute, dim3((unsigned)((p.slots + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, p);
+    hipLaunchKernelGGL(k_permute_advance, dim3(1), dim3(1), 0, s, a->state);
+    return spl_launched("k_permute");
 }
 
 static int64_t adam_chunks(int64_t numel) { return (numel + kChunk - 1) / kChunk; }

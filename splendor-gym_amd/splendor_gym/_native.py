@@ -163,6 +163,19 @@ class PpoNetBwd(ctypes.Structure):
                 ("actor_grad", PpoMlp), ("critic_grad", PpoMlp), ("scratch", c_void_p)]
 
 
+PPO_PERMUTE = 1  # SPL_PPO_PERMUTE: spl_ppo_permute and spl_ppo_loss_dev, what a whole update as one graph needs
+
+
+class PpoPermState(ctypes.Structure):
+    """spl_ppo_perm_state_t (include/splendor_ppo.h)"""
+    _fields_ = [("seed", c_uint64), ("draw", c_uint64)]
+
+
+class PpoPermute(ctypes.Structure):
+    """spl_ppo_permute_t (include/splendor_ppo.h)"""
+    _fields_ = [("n", c_int64), ("B", c_int32), ("reserved", c_int32), ("state", c_void_p), ("out", c_void_p)]
+
+
 EVAL_ABI = 1                     # SPL_EVAL_ABI (include/splendor_eval.h)
 POLICY_GREEDY_V2, EVAL_KEEP = 3, -1  # SPL_POLICY_GREEDY_V2, SPL_EVAL_KEEP: spl_eval_scripted_act only
 EVAL_COLS = 8                      # wins, losses, draws, unfinished, sum turns, sum prestige, checks, illegal
@@ -274,6 +287,8 @@ SIGNATURES = {
     "spl_ppo_net_backward_tiled": ([c_int32, ctypes.POINTER(PpoNetBwd), c_void_p], c_int32),
     "spl_ppo_net_forward_bf16": ([c_int32, ctypes.POINTER(PpoNetFwd), c_void_p], c_int32),
     "spl_ppo_net_backward_bf16": ([c_int32, ctypes.POINTER(PpoNetBwd), c_void_p], c_int32),
+    "spl_ppo_permute": ([ctypes.POINTER(PpoPermute), c_void_p], c_int32),
+    "spl_ppo_loss_dev": ([c_int32, ctypes.POINTER(PpoLoss), c_void_p, c_void_p], c_int32),
     # include/splendor_eval.h
     "spl_eval_abi_version": ([], c_int32),
     "spl_eval_scripted_act": ([c_int32, ctypes.POINTER(EvalAct), c_void_p], c_int32),
@@ -283,9 +298,10 @@ SIGNATURES = {
 }
 
 # what a library built from an earlier header may lack (SPLENDOR_AMD_LIB can name one): it still loads, and
-# what needs these asks has_net_tiled() / has_net_bf16() first
+# what needs these asks has_net_tiled() / has_net_bf16() / has_permute() first
 OPTIONAL = ("spl_ppo_net_forward_tiled", "spl_ppo_net_backward_tiled")
 OPTIONAL_BF16 = ("spl_ppo_net_forward_bf16", "spl_ppo_net_backward_bf16")
+OPTIONAL_PERMUTE = ("spl_ppo_permute", "spl_ppo_loss_dev")
 
 
 class NativeError(RuntimeError):
@@ -314,7 +330,7 @@ def load_library():
                           "`python -c 'import __graft_entry__ as g; g.build()'` (no CPU fallback exists)")
     lib = ctypes.CDLL(path)
     for name, (argtypes, restype) in SIGNATURES.items():
-        if name in OPTIONAL + OPTIONAL_BF16 and not hasattr(lib, name):
+        if name in OPTIONAL + OPTIONAL_BF16 + OPTIONAL_PERMUTE and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
         fn.argtypes = argtypes
@@ -333,6 +349,11 @@ def has_net_tiled(lib):
 def has_net_bf16(lib):
     """the library exports spl_ppo_net_forward_bf16 / spl_ppo_net_backward_bf16 (SPL_PPO_NET_BF16)"""
     return all(hasattr(lib, name) for name in OPTIONAL_BF16)
+
+
+def has_permute(lib):
+    """the library exports spl_ppo_permute / spl_ppo_loss_dev (SPL_PPO_PERMUTE)"""
+    return all(hasattr(lib, name) for name in OPTIONAL_PERMUTE)
 
 
 def check(lib, code):

@@ -29,11 +29,18 @@ The head is torch autograd (the default), ``PPORolloutStore.loss`` behind the tw
     float32 accumulation and master weights (spl_ppo_net_forward_bf16 / spl_ppo_net_backward_bf16), other numbers;
   * ``DeviceAdam``  what follows the head as one device call per minibatch (spl_ppo_adam): the global-norm
     clip, torch.optim.Adam's step and the target-KL early stop, decided on the device, so that
-    ``ppo_update`` with it reads the device once per update instead of once per minibatch.
+    ``ppo_update`` with it reads the device once per update instead of once per minibatch;
+  * ``DevicePermutation``  an epoch's permutation drawn on the device (spl_ppo_permute) from a (seed, draw) block
+    that the draw itself advances, laid out so that every minibatch's slice is 16-byte aligned;
+    ``permutation_reference`` is the same permutation in numpy, for saying afterwards which positions a
+    minibatch held.  With it, a ``DeviceAdam`` and a ``DeviceNets``, ``ppo_update(graph=True)`` captures one
+    whole update (every epoch's draw and every minibatch) as one hipGraph and replays it on later calls.
 
-There is no CPU fallback for the store, ``DeviceAdam`` or ``DeviceNets``.
+There is no CPU fallback for the store, ``DeviceAdam``, ``DeviceNets`` or ``DevicePermutation``.
 """
 import ctypes
+
+import numpy as np
 
 from . import _native
 from ._native import NUM_ACTIONS, OBS_DIM, OBS_U8, PpoGae, PpoGather, PpoLoss, PpoLossOut, PpoRecord, check
@@ -59,6 +66,62 @@ def _positions(idx, device):
             idx.device != device or idx.numel() < 1:
         raise ValueError(f"idx must be a non-empty contiguous int64 [B] tensor on {device}")
     return idx.numel()
+
+
+def _philox4x32_x(c0, c1, c2, c3, k0, k1):
+    """The .x word of Philox4x32-10 (csrc/spl_rng.h) for uint64 arrays holding 32-bit words."""
+    M32 = np.uint64(0xFFFFFFFF)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & M32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & M32
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & M32, (k1 + np.uint64(0xBB67AE85)) & M32
+    return c0
+
+
+def permutation_positions(positions, n, seed, draw):
+    """Where spl_ppo_permute's permutation of 0 .. n-1 for (seed, draw) sends `positions` (integers in [0, n);
+    `draw` may be an array that broadcasts against them): int64, of the broadcast shape.  numpy only.  The
+    definition is include/splendor_ppo.h's: eight rounds of an alternating Feistel network over the bits that
+    hold n - 1, Philox4x32-10 keyed by the seed and counted by (half, round, draw) as the round function,
+    repeated while the value is not below n."""
+    n = int(n)
+    if not 1 <= n <= 2 ** 31 - 1:
+        raise ValueError("n must be in 1 .. 2^31 - 1")
+    pos, drw = np.broadcast_arrays(np.asarray(positions), np.asarray(draw, dtype=np.uint64))
+    if pos.size and (pos.min() < 0 or pos.max() >= n):
+        raise ValueError("positions must be in [0, n)")
+    x = pos.astype(np.uint64).ravel()
+    if n == 1:
+        return x.astype(np.int64).reshape(pos.shape)
+    U, M32 = np.uint64, np.uint64(0xFFFFFFFF)
+    d_lo, d_hi = drw.ravel() & M32, drw.ravel() >> U(32)
+    seed = int(seed) & (2 ** 64 - 1)
+    k0, k1 = U(seed & 0xFFFFFFFF), U(seed >> 32)
+    bits = max(2, (n - 1).bit_length())
+    a = bits // 2
+    b = bits - a
+    todo = np.arange(x.size)  # the elements still walking
+    while todo.size:
+        y, lo, hi = x[todo], d_lo[todo], d_hi[todo]
+        for r in range(8):
+            wl, wr = (b, a) if r % 2 == 0 else (a, b)
+            L, R = y >> U(wr), y & U((1 << wr) - 1)
+            f = _philox4x32_x(R, np.full_like(R, r), lo, hi, np.full_like(R, k0), np.full_like(R, k1))
+            y = (R << U(wl)) | ((L ^ f) & U((1 << wl) - 1))
+        x[todo] = y
+        todo = todo[y >= U(n)]
+    return x.astype(np.int64).reshape(pos.shape)
+
+
+def permutation_reference(n, seed, draw):
+    """The permutation of 0 .. n-1 that spl_ppo_permute (DevicePermutation.draw) writes for (seed, draw), bit
+    for bit, as int64 [n]: element i is the store position that place i of the epoch holds, and minibatch m of
+    size B is [m * B : (m + 1) * B].  numpy only, no GPU: a run's seed and DevicePermutation.counter() are
+    enough to say afterwards what every minibatch held."""
+    draw = int(draw)
+    if not 0 <= draw < 2 ** 64:
+        raise ValueError("draw must be in 0 .. 2^64 - 1")
+    return permutation_positions(np.arange(int(n), dtype=np.int64), n, seed, draw)
 
 
 class _OnDevice:
@@ -140,6 +203,8 @@ class PPORolloutStore(_OnDevice):
         self.std32 = self._stats.view(torch.float32)[11:12]
         self._scratch = z((int(check(self.lib, self.lib.spl_ppo_gae_scratch_bytes(T))) // 8,), torch.float64)
         self._loss_bufs = {}  # B -> the buffers of loss(): scratch, dlogits, dvalue, out, the call serial
+        self._loss_coef = z((4,), torch.float32)  # clip_coef, vclip, vf_coef, ent_coef where spl_ppo_loss_dev reads them
+        self.loss_coef = (0.0, 0.0, 0.0, 0.0)     # what the host last wrote there
 
     def _record(self, **kw):
         with self.torch.cuda.device(self.device):
@@ -233,8 +298,23 @@ class PPORolloutStore(_OnDevice):
             self._loss_bufs[B] = bufs
         return bufs
 
-    def _launch_loss(self, idx, logits, value, coef, normalize):
+    def set_loss_coef(self, clip_coef, vclip, vf_coef, ent_coef):
+        """The four coefficients into the device block that the device-coefficient loss entry (spl_ppo_loss_dev)
+        reads: one small asynchronous copy on the current stream.  Nothing of them is a kernel argument there, so
+        a captured loss call follows the block.  ent_coef is signed as spl_ppo_loss_t's is.  A negative
+        clip_coef, vclip or vf_coef is not refused here: the device then counts every row of a call as bad."""
+        t = self.torch
+        self.loss_coef = tuple(float(x) for x in (clip_coef, vclip, vf_coef, ent_coef))
+        self._loss_coef.copy_(t.tensor(self.loss_coef, dtype=t.float32), non_blocking=True)
+
+    def _launch_loss(self, idx, logits, value, coef, normalize, device_coef=False):
+        """device_coef: the coefficients are the device block's (set_loss_coef), `coef` is not read."""
         bufs = self._loss_buffers(idx.numel())
+        if device_coef:
+            if not _native.has_permute(self.lib):
+                raise RuntimeError(f"the device coefficient block needs spl_ppo_loss_dev (SPL_PPO_PERMUTE), which "
+                                   f"{_native.lib_path()} does not export; rebuild the library")
+            coef = (0.0, 0.0, 0.0, 0.0)
         a = PpoLoss(K=self.num_steps, T=self.num_envs, normalize=1 if normalize else 0, reserved=0,
                     idx=idx.data_ptr(), mask_bits=self.mask_bits.data_ptr(), action=self.action.data_ptr(),
                     logprob=self.logprob.data_ptr(), value=self.value.data_ptr(), adv=self.adv.data_ptr(),
@@ -243,7 +323,10 @@ class PPORolloutStore(_OnDevice):
                     dlogits=bufs["dlogits"].data_ptr(), dvalue=bufs["dvalue"].data_ptr(),
                     out=bufs["out"].buf.data_ptr(), errors=self.errors.data_ptr(), scratch=bufs["scratch"].data_ptr())
         with self.torch.cuda.device(self.device):
-            check(self.lib, self.lib.spl_ppo_loss(idx.numel(), ctypes.byref(a), self._stream()))
+            if device_coef:
+                check(self.lib, self.lib.spl_ppo_loss_dev(idx.numel(), ctypes.byref(a), self._loss_coef.data_ptr(), self._stream()))
+            else:
+                check(self.lib, self.lib.spl_ppo_loss(idx.numel(), ctypes.byref(a), self._stream()))
         bufs["serial"] += 1
         return bufs
 
@@ -680,6 +763,73 @@ class DeviceNets(_OnDevice):
         bufs["idx"] = idx
 
 
+class DevicePermutation(_OnDevice):
+    """An epoch's permutation of `total` store positions drawn on the device (spl_ppo_permute,
+    include/splendor_ppo.h) and cut into minibatches of `batch_size` (at most `total`), the last one shorter.
+    The state block (seed, draw) lives on the device and draw() advances it there, so a captured draw() gives
+    the next permutation on every replay; the permutation for (seed, draw) is permutation_reference's.
+
+    The buffer is [ceil(total / B)][B rounded up to even] int64, the pad word of a row and the last row's tail
+    -1, so every view of minibatches() starts 16-byte aligned and DeviceNets never clones it.  A device
+    permutation is another permutation than torch.randperm's: a run that switches to it is another run."""
+
+    def __init__(self, total, batch_size, device, seed=0):
+        torch = _native.require_gpu()
+        self.torch, self.lib = torch, _native.load_library()
+        if not _native.has_permute(self.lib):
+            raise RuntimeError(f"DevicePermutation needs spl_ppo_permute (SPL_PPO_PERMUTE), which {_native.lib_path()} "
+                               "does not export; rebuild the library")
+        self.total = int(total)
+        if not 1 <= self.total <= 2 ** 31 - 1:
+            raise ValueError("total must be in 1 .. 2^31 - 1")
+        if int(batch_size) < 1:
+            raise ValueError("batch_size must be positive")
+        self.batch_size = B = min(int(batch_size), self.total)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("DevicePermutation lives on a GPU (no CPU fallback)")
+        self.rows, self.stride = (self.total + B - 1) // B, (B + 1) // 2 * 2
+        self._state = torch.zeros(2, dtype=torch.int64, device=self.device)  # spl_ppo_perm_state_t: seed, draw
+        self._buf = torch.full((self.rows, self.stride), -1, dtype=torch.int64, device=self.device)
+        last = self.total - (self.rows - 1) * B
+        self._views = [self._buf[r, :B if r < self.rows - 1 else last] for r in range(self.rows)]
+        self._args = _native.PpoPermute(n=self.total, B=B, reserved=0, state=self._state.data_ptr(), out=self._buf.data_ptr())
+        self.set_seed(seed)
+
+    @staticmethod
+    def _word(x):
+        x = int(x) & (2 ** 64 - 1)  # the uint64 word as the int64 torch holds
+        return x - 2 ** 64 if x >= 2 ** 63 else x
+
+    def set_seed(self, seed):
+        """Asynchronous."""
+        self.seed = int(seed) & (2 ** 64 - 1)
+        self._state[0:1].fill_(self._word(seed))
+
+    def set_counter(self, draw):
+        """The draw counter the next draw() uses, e.g. a resumed run's (asynchronous)."""
+        self._state[1:2].fill_(self._word(draw))
+
+    def counter(self):
+        """The draw counter: how many draw() calls and replays of one this state has seen since 0
+        (synchronises)."""
+        return int(self._state[1].item()) & (2 ** 64 - 1)
+
+    def draw(self):
+        """The next permutation into the buffer behind minibatches(); the counter advances by one on the device
+        (one spl_ppo_permute call, asynchronous)."""
+        with self.torch.cuda.device(self.device):
+            check(self.lib, self.lib.spl_ppo_permute(ctypes.byref(self._args), self._stream()))
+
+    def minibatches(self):
+        """The fixed list of views of the buffer, one per minibatch: contiguous int64, 16-byte aligned, holding
+        whatever the latest draw() wrote."""
+        return list(self._views)
+
+
+GRAPH_MAX_MINIBATCHES = 1024  # ppo_update(graph=True): update_epochs x minibatches per epoch at the most
+
+
 class _Lazy:
     """Attributes given as functions without arguments, each evaluated when it is first read, and kept."""
 
@@ -763,7 +913,7 @@ class _DeviceAdamStep:
 
 def ppo_update(agent, optimizer, store, clip_coef=0.2, vclip=0.2, ent_coef=0.03, vf_coef=0.5, update_epochs=4,
                minibatch_size=256, target_kl=0.02, max_grad_norm=0.5, generator=None, entropy_bonus=False,
-               fused_loss=False, device_nets=False):
+               fused_loss=False, device_nets=False, permutation=None, graph=False):
     """The update of ppo_splendor.py:327-361 over store.minibatches (call store.compute_gae first):
     clipped policy loss, clipped value loss, the entropy term, grad-norm clip at 0.5 and the target-KL
     early stop, which like the reference's `break` ends the current epoch only.
@@ -795,10 +945,50 @@ def ppo_update(agent, optimizer, store, clip_coef=0.2, vclip=0.2, ent_coef=0.03,
     first minibatch's, evaluated before any optimiser step) and optimizer_steps; with the fused or the nets
     head also the last minibatch's clipfrac.  With a DeviceAdam the dictionary is filled from the device
     (optimizer_steps = the applied steps, the statistics those of the last applied step, first_approx_kl
-    that of the first), plus gated (skipped minibatches) and grad_norm (the last call's)."""
+    that of the first), plus gated (skipped minibatches) and grad_norm (the last call's).
+
+    The permutation.  By default store.minibatches: torch.randperm from `generator`, once per epoch.
+    permutation=DevicePermutation(K * T, minibatch_size, device, seed): every epoch calls permutation.draw()
+    and walks its views instead, with any head and either optimiser; `generator` is then not used, and the
+    minibatches are permutation_reference's for the counters the update passed through.  Another permutation
+    than torch.randperm's, so another run.
+
+    graph=True (needs a DeviceAdam, device_nets=a DeviceNets object and a DevicePermutation; ValueError
+    otherwise) runs the first call eagerly, then captures one whole update on one stream (begin_update; per
+    epoch begin_epoch, draw and every minibatch's forward, loss, backward and step) as one linear hipGraph,
+    and later calls replay it.  Everything that changes between updates is read from device memory: the draw
+    counter, the optimiser's state block (set_lr, max_grad_norm and target_kl are followed) and the four loss
+    coefficients, which go through store.set_loss_coef and the device-coefficient loss entry, in the eager
+    first call too.  The numbers are those of graph=False with the same permutation, bit for bit.  The
+    capture is kept on the store, keyed by what is baked into it (the objects, K, T, minibatch_size,
+    update_epochs, the nets' tiled and operands); a changed key captures again.  store._update_replays counts
+    the replays since the capture.  More than GRAPH_MAX_MINIBATCHES minibatches an update is refused."""
     torch = store.torch
-    if int(update_epochs) < 1:
+    epochs = int(update_epochs)
+    if epochs < 1:
         raise ValueError("update_epochs must be at least 1")
+    if graph:  # refused before anything is built or launched
+        if not isinstance(optimizer, DeviceAdam):
+            raise ValueError("ppo_update(graph=True) needs a DeviceAdam as the optimizer: a torch.optim step reads the "
+                             "minibatch's KL on the host, which a replayed graph cannot do")
+        if not isinstance(device_nets, DeviceNets):
+            raise ValueError("ppo_update(graph=True) needs device_nets=a DeviceNets object (the nets head, with buffers that "
+                             "live from update to update): autograd builds its own graph on every call")
+        if not isinstance(permutation, DevicePermutation):
+            raise ValueError("ppo_update(graph=True) needs permutation=a DevicePermutation: torch.randperm's generator "
+                             "does not advance inside a replayed graph")
+    if permutation is not None:
+        total = store.num_steps * store.num_envs
+        if not isinstance(permutation, DevicePermutation):
+            raise ValueError("permutation must be a DevicePermutation or None")
+        if permutation.total != total or permutation.batch_size != min(int(minibatch_size), total) or \
+                permutation.device != store.device:
+            raise ValueError(f"the DevicePermutation is for {permutation.total} positions in minibatches of "
+                             f"{permutation.batch_size} on {permutation.device}, the update for {total} in minibatches of "
+                             f"{min(int(minibatch_size), total)} on {store.device}")
+        if graph and epochs * permutation.rows > GRAPH_MAX_MINIBATCHES:
+            raise ValueError(f"ppo_update(graph=True) captures at most GRAPH_MAX_MINIBATCHES = {GRAPH_MAX_MINIBATCHES} "
+                             f"minibatches an update, not {epochs} epochs x {permutation.rows}")
     nets = None
     if device_nets is not False and device_nets is not None:
         nets = device_nets if isinstance(device_nets, DeviceNets) else DeviceNets(agent)
@@ -842,14 +1032,48 @@ def ppo_update(agent, optimizer, store, clip_coef=0.2, vclip=0.2, ent_coef=0.03,
 
     def nets_head(idx):
         logits, value = nets.forward(store, idx)
-        bufs = store._launch_loss(idx, logits, value, coef, True)
+        bufs = store._launch_loss(idx, logits, value, coef, True, device_coef=bool(graph))
         nets.backward(store, idx, bufs["dlogits"], bufs["dvalue"])  # overwrites every p.grad: no zero_grad
         return bufs["out"]
 
     head = nets_head if nets is not None else fused_head if fused_loss else torch_head
-    for _ in range(int(update_epochs)):
-        stepper.begin_epoch()
-        for idx in store.minibatches(minibatch_size, generator):
-            if not stepper.step(head(idx)):
-                break
-    return stepper.result()
+
+    def epoch_minibatches():
+        if permutation is None:
+            return store.minibatches(minibatch_size, generator)
+        permutation.draw()
+        return permutation.minibatches()
+
+    def update():
+        for _ in range(epochs):
+            stepper.begin_epoch()
+            for idx in epoch_minibatches():
+                if not stepper.step(head(idx)):
+                    break
+
+    if not graph:
+        update()
+        return stepper.result()
+    # the coefficients, like max_grad_norm and target_kl in the stepper above, are written where they differ from
+    # what the device holds, outside the graph
+    if store.loss_coef != coef:
+        store.set_loss_coef(*coef)
+    key = (id(agent), id(optimizer), id(nets), id(permutation), store.num_steps, store.num_envs, permutation.batch_size,
+           epochs, True, nets.tiled, nets.operands)
+    cached = getattr(store, "_update_graph", None)
+    if cached is not None and cached[0] == key:
+        stepper.with_clipfrac = True  # the nets head's statistics, as in the eager call
+        cached[1].replay()
+        store._update_replays += 1
+        return stepper.result()
+    # as collect(graph=True): the first call runs eagerly (it loads every kernel and sizes every per-B buffer, which
+    # a capture must not do) and then captures the same update for the calls after it; capturing runs nothing
+    update()
+    res = stepper.result()  # synchronises
+    torch.cuda.synchronize(store.device)
+    stepper.epochs = 0
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        update()
+    store._update_graph, store._update_replays = (key, g, agent, optimizer, nets, permutation), 0
+    return res

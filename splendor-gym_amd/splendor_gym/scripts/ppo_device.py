@@ -12,7 +12,11 @@ backward passes as device calls too, a minibatch then being four device calls; -
 passes by the LDS-tiled matrix-core kernels built for minibatches of tens of thousands of rows, always or
 from DeviceNets.TILED_MIN_ROWS rows upward, with the same bytes either way; --net-operands bf16: those
 passes with bf16 operands on the matrix cores at every minibatch size, float32 accumulation and master
-weights, which is another run: its numbers differ).  After each update the
+weights, which is another run: its numbers differ; --device-permutation: each epoch's permutation drawn on the
+device by splendor_gym.ppo.DevicePermutation seeded with --seed instead of torch.randperm, another permutation and
+so another run; --graph-update: the whole update, every epoch's draw and every minibatch, captured once and
+replayed as one hipGraph, which implies --device-permutation, --device-adam and --device-nets and gives the
+numbers of those three without it).  After each update the
 fused agent and the pool re-pack the new weights; every --snapshot-every-updates updates the pool takes
 a snapshot.  --eval-every-updates N evaluates before training and every N updates, --eval-games games
 against each of random, greedy_v1, basic, the agent itself and greedy_v2 in one batch on the device
@@ -63,17 +67,26 @@ def main(argv=None):
     p.add_argument("--net-operands", choices=("f32", "bf16"), default="f32",
                    help="DeviceNets' matrix products: f32, or bf16 operands with float32 accumulation and float32 master "
                         "weights (mixed precision: the numbers of the run change); bf16 implies --device-nets")
-    p.add_argument("--no-graph", action="store_true", help="run every rollout eagerly instead of replaying a hipGraph")
+    p.add_argument("--device-permutation", action="store_true",
+                   help="draw each epoch's permutation on the device (splendor_gym.ppo.DevicePermutation, seeded with --seed) "
+                        "instead of torch.randperm: another permutation, so another run")
+    p.add_argument("--graph-update", action="store_true",
+                   help="capture one whole update (every epoch's permutation and every minibatch) as one hipGraph and replay "
+                        "it; implies --device-permutation, --device-adam and --device-nets; --no-graph runs it eagerly")
+    p.add_argument("--no-graph", action="store_true",
+                   help="run every rollout (and with --graph-update every update) eagerly instead of replaying a hipGraph")
     p.add_argument("--eval-every-updates", type=int, default=0,
                    help="evaluate before training and every N updates (0: never), as ppo_splendor.py does")
     p.add_argument("--eval-games", type=int, default=400, help="games per opponent kind of one evaluation")
     args = p.parse_args(argv)
-    args.device_nets = args.device_nets or args.tiled_nets != "off" or args.net_operands != "f32"
+    args.device_nets = args.device_nets or args.tiled_nets != "off" or args.net_operands != "f32" or args.graph_update
+    args.device_adam = args.device_adam or args.graph_update
+    args.device_permutation = args.device_permutation or args.graph_update
 
     import torch
     from ..fused_policy import FusedActorCritic, OpponentPool
     from ..policy import ActorCritic
-    from ..ppo import DeviceAdam, DeviceNets, PPORolloutStore, collect, ppo_update
+    from ..ppo import DeviceAdam, DeviceNets, DevicePermutation, PPORolloutStore, collect, ppo_update
     from ..selfplay import DualStepVectorEnv
 
     dev = torch.device(args.device)
@@ -98,6 +111,8 @@ def main(argv=None):
                             agent_obs_u8=True)
     store = PPORolloutStore(args.num_steps, args.num_envs, dev)
     gen = torch.Generator(device=dev).manual_seed(args.seed)
+    perm = DevicePermutation(args.num_steps * args.num_envs, args.minibatch_size, dev, seed=args.seed) \
+        if args.device_permutation else None
     obs, info = env.reset(seed=args.seed)
     mask = info["action_mask"]
     batch = args.num_envs * args.num_steps
@@ -131,7 +146,8 @@ def main(argv=None):
                          ent_coef=args.ent_coef + (args.ent_coef_final - args.ent_coef) * progress,
                          vf_coef=args.vf_coef, update_epochs=args.update_epochs, minibatch_size=args.minibatch_size,
                          target_kl=args.target_kl, generator=gen, entropy_bonus=args.entropy_bonus,
-                         fused_loss=args.fused_loss, device_nets=nets)
+                         fused_loss=args.fused_loss, device_nets=nets, permutation=perm,
+                         graph=args.graph_update and not args.no_graph)
         agent_k.refresh()
         pool.refresh()
         if (update + 1) % max(1, args.snapshot_every_updates) == 0:

@@ -1,7 +1,7 @@
 """Timings of the PPO rollout store (splendor_gym/ppo.py) at the size the engine exists for.
 
     python tools/bench_ppo.py [--tables 65536] [--steps 128] [--repeats 7] [--loss-json FILE] [--adam-json FILE] [--adam-only]
-                                [--nets-json FILE] [--nets-only]
+                                [--nets-json FILE] [--nets-only] [--graph-json FILE] [--graph-only]
 
 Prints one JSON line with five comparisons, each arm timed with device events, the arms alternating,
 medians reported:
@@ -26,6 +26,11 @@ medians reported:
      B = 256, 4 096, 16 384 and 65 536; and one whole ppo_update(fused_loss=True, target_kl=0.02) with
      DeviceAdam without device_nets, with them, with the tiled ones and with the bf16 ones, at the same two
      shapes as in 5 (--nets-json profiles/ppo/bench_ppo_nets_bf16.json keeps the section).
+  7. graph (--graph-only, not part of the default run): one whole ppo_update with DeviceAdam and DeviceNets, target
+     KL 0.02, 4 epochs, eager with torch.randperm, eager with a DevicePermutation and as the replayed graph
+     (ppo_update(graph=True)), at 128 x 16 with minibatch 256 (the 8-row f32 passes) and at 128 x 4 096 with
+     minibatch 65 536 (tiled="auto", and again with operands="bf16"), host clock; and spl_ppo_permute alone at
+     n = 2 048, 524 288 and 8 388 608 (--graph-json profiles/ppo/bench_ppo_graph.json keeps the section).
 Bytes are the algorithmic bytes each kernel has to move, computed from the shapes below.
 """
 import argparse
@@ -49,6 +54,8 @@ def main():
     ap.add_argument("--adam-only", action="store_true", help="run the optimiser section alone")
     ap.add_argument("--nets-json", default="", help="also write the network section to this file (profiles/ppo/bench_ppo_nets_bf16.json)")
     ap.add_argument("--nets-only", action="store_true", help="run the network-pass section alone")
+    ap.add_argument("--graph-json", default="", help="also write the graph section to this file (profiles/ppo/bench_ppo_graph.json)")
+    ap.add_argument("--graph-only", action="store_true", help="run the whole-update-as-one-graph section alone")
     args = ap.parse_args()
 
     import torch
@@ -337,6 +344,111 @@ def main():
                            "repeats": args.repeats, "nets": section}, f, indent=1)
                 f.write("\n")
         return section
+
+    # ---- 7. one update as one replayed graph (--graph-only runs nothing else) ------------------------
+    def graph_section():
+        import copy
+        import time
+        from splendor_gym.ppo import DeviceAdam, DeviceNets, DevicePermutation, collect, ppo_update
+
+        trained = net()
+
+        def collected(tables, steps):
+            counter = torch.zeros(1, dtype=torch.int64, device=dev)
+            e = DualStepVectorEnv(tables, device=dev, opponent="random", policy_seed=3, opponent_obs=False,
+                                  step_counter=counter, agent_obs_u8=True)
+            obs, info = e.reset(seed=40)
+            s = PPORolloutStore(steps, tables, dev)
+            collect(e, FusedActorCritic(trained), s, obs, info["action_mask"], seed=5)
+            s.compute_gae()
+            e.close()
+            return s
+
+        def update_arms(store, minibatch, **nets_kw):
+            total = store.num_steps * store.num_envs
+
+            def arm(permutation, graph):
+                # the objects live from update to update, as a training run's do; every timed update starts from the
+                # checkpoint, zero moments and draw counter 0, restored outside the clock, so that every window of an
+                # arm does the same work and the two device-permutation arms the same arithmetic
+                a = copy.deepcopy(trained)
+                opt = DeviceAdam(list(a.parameters()), lr=2.5e-4, eps=1e-5)
+                nets = DeviceNets(a, **nets_kw)
+                perm = DevicePermutation(total, minibatch, dev, seed=0) if permutation else None
+
+                def run():
+                    with torch.no_grad():
+                        for p, q in zip(a.parameters(), trained.parameters()):
+                            p.copy_(q)
+                    opt._exp_avg.zero_()
+                    opt._exp_avg_sq.zero_()
+                    opt._set("step", 0, integer=True)
+                    if perm is not None:
+                        perm.set_counter(0)
+                    g = torch.Generator(device=dev).manual_seed(0)
+                    torch.cuda.synchronize(dev)
+                    t0 = time.perf_counter()
+                    res = ppo_update(a, opt, store, update_epochs=4, minibatch_size=minibatch, target_kl=0.02, generator=g,
+                                     device_nets=nets, permutation=perm, graph=graph)
+                    torch.cuda.synchronize(dev)
+                    return (time.perf_counter() - t0) * 1e3, res
+                return run
+
+            runs = {"eager_randperm": arm(False, False), "eager_device_permutation": arm(True, False),
+                    "graph": arm(True, True)}
+            for fn in runs.values():  # the graph arm's first call is its eager run and the capture
+                fn()
+            times, last = {k: [] for k in runs}, {}
+            for _ in range(args.repeats):
+                for name, fn in runs.items():
+                    t, last[name] = fn()
+                    times[name].append(t)
+            out = {}
+            for name in runs:
+                out[f"{name}_ms"] = round(statistics.median(times[name]), 3)
+                out[f"{name}_ms_fastest_slowest"] = [round(min(times[name]), 3), round(max(times[name]), 3)]
+                out[f"{name}_optimizer_steps"] = last[name]["optimizer_steps"]
+                out[f"{name}_gated"] = last[name]["gated"]
+            same = all(last["graph"][k] == last["eager_device_permutation"][k] for k in last["graph"])
+            out.update({"ratio_eager_randperm_over_graph": round(out["eager_randperm_ms"] / out["graph_ms"], 3),
+                        "ratio_eager_device_permutation_over_graph": round(out["eager_device_permutation_ms"] / out["graph_ms"], 3),
+                        "faster": min(runs, key=lambda name: out[f"{name}_ms"]), "graph_result_equals_eager_device_permutation": same,
+                        "replays": store._update_replays, "minibatches_run": 4 * -(-total // minibatch),
+                        "K": store.num_steps, "T": store.num_envs, "minibatch": minibatch, "epochs": 4,
+                        "nets": {"tiled": nets_kw.get("tiled", False), "operands": nets_kw.get("operands", "f32")}})
+            return out
+
+        big = collected(4096, 128)
+        updates = {"reference_shape": update_arms(collected(16, 128), 256),
+                   "large": update_arms(big, 65536, tiled="auto"),
+                   "large_bf16": update_arms(big, 65536, tiled="auto", operands="bf16")}
+        updates["note"] = ("one ppo_update(device_nets=DeviceNets, target_kl=0.02, 4 epochs) with DeviceAdam from the trained checkpoint: "
+                           "eager over torch.randperm, eager over a DevicePermutation, and ppo_update(graph=True) replaying its "
+                           "capture; the objects are built once per arm and every timed update starts from the checkpoint with zero "
+                           "moments, restored outside the clock; host clock from the call to a device synchronise behind it (the "
+                           "result dictionary's read-back included), arms alternating in one process, medians")
+        permute = {}
+        for n, B in ((2048, 256), (524288, 65536), (8388608, 65536)):
+            perm = DevicePermutation(n, B, dev, seed=0)
+            spread = {}
+            ms = timed({"permute": perm.draw}, inner=100 if n <= 524288 else 20, spread=spread)
+            permute[f"n{n}"] = {"us": round(ms["permute"] * 1e3, 2), "us_fastest_slowest": [round(x * 1e3, 2) for x in spread["permute"]],
+                                "B": B, "bytes": perm.rows * perm.stride * 8,
+                                "GBps": round(perm.rows * perm.stride * 8 / (ms["permute"] * 1e-3) / 1e9, 1)}
+        permute["note"] = ("DevicePermutation.draw (spl_ppo_permute: the permutation's launch and the one-thread launch that advances "
+                           "the counter), device events around back-to-back eager calls, medians; bytes: the int64 words written")
+        section = {"ppo_update": updates, "permute": permute}
+        if args.graph_json:
+            with open(args.graph_json, "w") as f:
+                json.dump({"metric": "one PPO update as one replayed graph (ppo_update(graph=True)) beside the eager update, and "
+                                     "spl_ppo_permute, one MI355X", "repeats": args.repeats, "graph": section}, f, indent=1)
+                f.write("\n")
+        return section
+
+    if args.graph_only:
+        print(json.dumps({"metric": "one PPO update as one replayed graph, one MI355X", "repeats": args.repeats,
+                          "graph": graph_section()}))
+        return
 
     if args.nets_only:
         print(json.dumps({"metric": "PPO network passes, one MI355X", "repeats": args.repeats, "nets": nets_section()}))
