@@ -136,7 +136,12 @@ int spl_abi_version(void);
 const char *spl_last_error(void);
 
 /* cards: 90 x 8 int32 [tier, bonus colour, points, cost w,b,g,r,k];
- * nobles: 10 x 6 int32 [req w,b,g,r,k, points]   (splendor_gym/engine/data/tables.json) */
+ * nobles: 10 x 6 int32 [req w,b,g,r,k, points]   (splendor_gym/engine/data/tables.json)
+ * Any table pair within these ranges is accepted: tier 1..3, bonus colour 0..4, card points, noble
+ * points, costs and requirements 0..255 each (SPL_E_ARG otherwise), and
+ *   14 + max card points + max noble points <= 255   (SPL_E_RANGE otherwise):
+ * a player enters a move with at most 14 prestige and gains at most one card and one noble in it, and
+ * the packed state holds prestige in one byte.  Both checks run before any device work. */
 int spl_ctx_create(int device, const int32_t *cards, const int32_t *nobles, spl_ctx_t **out);
 int spl_ctx_destroy(spl_ctx_t *ctx);
 /* Pool refill period in steps (default 64; three pool deals per table cover three resets in between);

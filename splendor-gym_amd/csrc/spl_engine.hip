@@ -50,8 +50,13 @@ struct KTables {
     const uint4 *cards;   // [90] {1,tier,points,oh_w | oh_b..oh_k | cost w,b,g,r | cost k,colour,0,0}
     const uint2 *nobles;  // [10] {1,req w,b,g | req r,k,points,0}
     const uint4 *lut;     // [kLutEntries] token-return MT outputs (top 3 bits, 10 per word)
-    uint32_t mtag;        // this context's legal-mask cache tag (1..65535)
+    uint32_t mtag;        // this context's legal-mask cache tag (bits 0-15: 1..65535) | kTagFreeCard
 };
+// Bit 31 of KTables::mtag: the card table has a card of total cost 0, so a fresh deal may allow a purchase and
+// reset lanes evaluate legal_moves instead of taking kFreshDealMask.  Set at context creation; a kernel argument,
+// so the branch on it is wave-uniform, and it rides in the tag's word, so it costs the kernels no register.
+constexpr uint32_t kTagFreeCard = 1u << 31;
+__device__ __forceinline__ bool has_free_card(const KTables &Tb) { return (Tb.mtag & kTagFreeCard) != 0u; }
 
 struct KStep {
     const int32_t *actions;
@@ -555,7 +560,10 @@ __device__ __forceinline__ uint32_t deck_pop(uint32_t *sw, uint32_t top, int t) 
 }
 
 // legal_moves of every fresh deal (engine/rules.py:40-93 on state.py:181-211's table): every
-// take-3 and take-2 (bank 4 of each colour), every visible and blind reserve, no purchase
+// take-3 and take-2 (bank 4 of each colour), every visible and blind reserve, no purchase — as long as
+// every card costs something.  A context whose card table has a free card (kTagFreeCard) never
+// publishes the constant: its reset lanes evaluate legal_moves of the dealt state (fresh_deal_mask,
+// or the deferred evaluation of step_ws).
 constexpr uint64_t kFreshDealMask = ((1ull << 15) - 1ull) | (((1ull << 15) - 1ull) << 27);
 
 // tier an action pops from: buy visible (:216-225) and reserve visible (:226-240) refill the
@@ -1463,7 +1471,9 @@ __device__ __forceinline__ void store_words(const Tab<P> &T, const KArena &A, in
 #pragma unroll
         for (int k = 0; k < 4; ++k) A.planes[(size_t)pw_index(q, k) * A.n + t] = T.pw[q][k];
 }
+// `tag`: KTables::mtag (the shift drops its flag bit) or 0
 __device__ __forceinline__ void store_legal(const KArena &A, int t, uint64_t legal, uint32_t tag) {
+    static_assert(kLegalTagShift == 16 && kLegalTagMax == 0xFFFFu, "the tag is the low half of KTables::mtag");
     A.legal[t] = (uint32_t)legal;
     A.legal[A.n + t] = ((uint32_t)(legal >> 32) & kLegalHiBits) | (tag << kLegalTagShift);
 }
@@ -1478,7 +1488,10 @@ struct LegalCache {
     uint32_t lo, hi;
     // tag 0 is "unknown" on both sides: an entry a crafted upload left, and a context without a tag of its
     // own (card_table_tag ran out) never trusts an entry
-    __device__ __forceinline__ bool known(uint32_t tag) const { return tag != 0u && (hi >> kLegalTagShift) == tag; }
+    // (`tag`: KTables::mtag, its flag bit above the tag ignored)
+    __device__ __forceinline__ bool known(uint32_t tag) const {
+        return (tag & kLegalTagMax) != 0u && (hi >> kLegalTagShift) == (tag & kLegalTagMax);
+    }
     __device__ __forceinline__ uint64_t mask() const { return (uint64_t)lo | ((uint64_t)(hi & kLegalHiBits) << 32); }
 };
 __device__ __forceinline__ LegalCache load_legal(const KArena &A, int t) {
@@ -1715,6 +1728,14 @@ __device__ __forceinline__ void autoreset_table(Tab<P> &T, const KArena &A, int 
     pool_dirty |= flip_to_pool<P>(T, A, t, pool, scr, mtx, o.flags);
     o.flags |= SPL_F_RESET;
     o.mask = kFreshDealMask;
+}
+
+// The step mask of a lane whose table was just re-dealt (o.flags carries SPL_F_RESET; autoreset_table and
+// dealer_step left kFreshDealMask): under a card table with a free card, legal_moves of the dealt state.
+// The branch on the table's flag is wave-uniform (a kernel argument); other contexts do no work here.
+template <int P>
+__device__ __forceinline__ void fresh_deal_mask(StepOut &o, const Tab<P> &T, const Consts &L, const KTables &Tb) {
+    if (has_free_card(Tb) && (o.flags & SPL_F_RESET)) o.mask = legal_of(T, L);
 }
 
 // Terminal rows staged in L.frows (bits of `fin`) -> final_obs rows of this wave.
@@ -1961,6 +1982,7 @@ __global__ __launch_bounds__(64) void k_rollout(KArena A, KTables Tb, KStep S, i
         }
         if (valid && o.term && S.autoreset)
             autoreset_table(T, A, t, pool, &L.rows[lane * kScratchStride], deal_mtx, o, pool_dirty);
+        fresh_deal_mask(o, T, L, Tb);
         wave_lds_sync();
         if (!abl(ABL_ENCODE)) encode_row(T, L.rows, L);
         L.mask[lane] = o.mask;
@@ -2281,7 +2303,10 @@ __device__ __forceinline__ void step_ws(StepWsLDS<P> &L, KArena A, KTables Tb, K
             autoreset_table(T, A, t, pool, &L.rows[lane * kScratchStride], mtx, o, pool_dirty);
 #pragma unroll
         for (int w = 0; w < kW; ++w) L.st[w][lane] = tab_word(T, w);
-        if (!kRulesMask) L.omask[lane] = o.mask;  // the tail / output wave evaluates the deferred lanes' masks
+        // a free card in the table (wave-uniform): the re-dealt lanes' masks are legal_moves of the dealt
+        // state, evaluated with the other lanes' deferred ones by whichever wave takes the masks
+        const bool redealt = has_free_card(Tb) && (o.flags & SPL_F_RESET) != 0u;
+        if (!kRulesMask) L.omask[lane] = redealt ? kMaskDeferred : o.mask;  // the tail / output wave evaluates the deferred lanes' masks
         STAMP(3);
         ws_sync();  // hand-off 1: state words (deal scratch in `rows` free again)
         // this wave encodes the first half of every row while the output wave encodes the second
@@ -2304,7 +2329,7 @@ __device__ __forceinline__ void step_ws(StepWsLDS<P> &L, KArena A, KTables Tb, K
         STAMP(7);
         STAMPV(9, __popcll(fin_all) | (__popcll(__ballot((o.mask & kMaskDeferred) != 0)) << 8));
         if (kRulesMask) {
-            o.mask = resolved_mask(o.mask, T, L, (uint64_t)action);
+            o.mask = resolved_mask(redealt ? kMaskDeferred : o.mask, T, L, (uint64_t)action);
             STAMP(5);
             // masks and small outputs leave from this wave while the output wave streams the rows
             store_step_mask(L, S, o.mask, t0, rows);
@@ -3136,6 +3161,7 @@ __device__ __forceinline__ void rules_wave(LdsT &L, const KArena &A, const KTabl
             if (valid && o.term && S.autoreset)
                 autoreset_table(T, A, t, pool, L.scratch(b, lane), L.deal_mtx(b), o, pool_dirty);
         }
+        fresh_deal_mask(o, T, L, Tb);
         st.at(7, k);
         L.small[b][lane] = pack_small(valid, o, wnr, valid && o.term, ep_add);  // stored by the output wave
         if (kDealer && S.policy == SPL_POLICY_UNIFORM && k >= 2) {
@@ -3841,6 +3867,7 @@ struct spl_ctx_s {
     int deleg_every;     // spl_rollout per-step store: rollout-store delegation every n-th step (0 = off)
     int partner_lead;    // per-step store partner hand-off lead in steps (0 off, < 0 forced)
     uint32_t mtag;         // legal-mask cache tag of this context's card table (card_table_tag), 1..65535, or 0
+    uint32_t free_card;    // 1 when a card of the table costs nothing (kTagFreeCard of KTables::mtag)
     int step_tail;         // spl_step shape: -1 auto (the tail wave up to step_tail_blocks workgroups), 0 two waves, 1 three
     int64_t step_tail_blocks;
     uint64_t *fault_host;  // host-mapped, fine-grained: the serial of a launch that faulted (0 = none), spl_ctx_faults
@@ -3865,7 +3892,9 @@ static inline int fail(int code, const std::string &msg) { return spl_fail(code,
         if (e_ != hipSuccess) return fail(SPL_E_HIP, std::string(#expr ": ") + hipGetErrorString(e_)); \
     } while (0)
 
-static KTables ktables(const spl_ctx_t *c) { return KTables{c->cards, c->nobles, c->lut, c->mtag}; }
+static KTables ktables(const spl_ctx_t *c) {
+    return KTables{c->cards, c->nobles, c->lut, c->mtag | (c->free_card ? kTagFreeCard : 0u)};
+}
 
 static int check_arena(const spl_ctx_t *ctx, const spl_arena_t *a) {
     if (!ctx) return fail(SPL_E_ARG, "null context");
@@ -3981,6 +4010,8 @@ int spl_ctx_create(int device, const int32_t *cards, const int32_t *nobles, spl_
     *out = nullptr;
     // constant records: observation-ready card bytes (engine/encode.py:77-96) + costs
     std::vector<uint4> crec(90);
+    bool free_card = false;
+    int max_card_points = 0, max_noble_points = 0;
     for (int i = 0; i < 90; ++i) {
         const int32_t *c = cards + 8 * i;
         if (c[0] < 1 || c[0] > 3 || c[1] < 0 || c[1] > 4 || c[2] < 0 || c[2] > 255)
@@ -3995,6 +4026,8 @@ int spl_ctx_create(int device, const int32_t *cards, const int32_t *nobles, spl_
             b[8 + k] = (uint8_t)c[3 + k];
         }
         b[13] = (uint8_t)c[1];
+        free_card |= c[3] + c[4] + c[5] + c[6] + c[7] == 0;
+        max_card_points = std::max(max_card_points, (int)c[2]);
         memcpy(&crec[i], b, 16);
     }
     std::vector<uint2> nrec(10);
@@ -4006,9 +4039,17 @@ int spl_ctx_create(int device, const int32_t *cards, const int32_t *nobles, spl_
             if (n[k] < 0 || n[k] > 255) return fail(SPL_E_ARG, "bad noble table");
             b[1 + k] = (uint8_t)n[k];
         }
+        if (n[5] < 0 || n[5] > 255) return fail(SPL_E_ARG, "bad noble points");
         b[6] = (uint8_t)n[5];
+        max_noble_points = std::max(max_noble_points, (int)n[5]);
         memcpy(&nrec[i], b, 8);
     }
+    // a player enters a move with at most 14 prestige (15 ends the game) and gains at most one card and
+    // one noble in it: the largest value the prestige byte of the packed player words has to hold
+    if (14 + max_card_points + max_noble_points > 255)
+        return fail(SPL_E_RANGE, "card and noble points overflow the prestige byte: 14 + max card points (" +
+                                     std::to_string(max_card_points) + ") + max noble points (" +
+                                     std::to_string(max_noble_points) + ") must not exceed 255");
     HIP_TRY(hipSetDevice(device));
     int resident[7][5] = {};
     {
@@ -4025,6 +4066,7 @@ int spl_ctx_create(int device, const int32_t *cards, const int32_t *nobles, spl_
     spl_ctx_t *c = new spl_ctx_t();
     c->device = device;
     c->mtag = card_table_tag(crec, nrec);
+    c->free_card = free_card ? 1u : 0u;
     c->refill_period = 64;
     c->refill_fused = 1;
     c->deleg_every = kDelegEveryDefault;

@@ -34,7 +34,8 @@ class Engine:
     DEFAULT_REFILL = {2: 64, 3: 32, 4: 16}
 
     def __init__(self, num_tables, num_players=2, device=None, refill_period=None, table0=0, refill_fused=True,
-                 pipeline=True, delegation=None, cards=None, partner_lead=None, host_io=False, step_tail=None):
+                 pipeline=True, delegation=None, cards=None, partner_lead=None, host_io=False, step_tail=None,
+                 nobles=None):
         torch = _native.require_gpu()
         self.torch = torch
         self.lib = _native.load_library()
@@ -50,7 +51,7 @@ class Engine:
         self._step_tail = step_tail
         self.ctx = None
         self._fault_carry = 0  # a fault seen on a context replaced by set_card_table
-        self._create_ctx(cards)
+        self._create_ctx(cards, nobles)
         nbytes = int(self.lib.spl_arena_bytes(self.n, self.P))
         dev = self.device
         self._arena_raw = torch.zeros(nbytes + 256, dtype=torch.uint8, device=dev)
@@ -94,22 +95,27 @@ class Engine:
         check(self.lib, self.lib.spl_host_mapped(ctypes.c_void_p(ptr), ctypes.byref(same)))
         return bool(same.value)
 
-    def _create_ctx(self, cards=None):
-        """A library context over the card table `cards` (int32 [90, 8]; None = the canonical
-        engine/data/tables.json) and the canonical nobles, with this engine's settings."""
+    def _create_ctx(self, cards=None, nobles=None):
+        """A library context over the card table `cards` (int32 [90, 8]) and the noble table `nobles`
+        (int32 [10, 6]; None = the canonical engine/data/tables.json for either), with this engine's
+        settings."""
         torch = self.torch
-        base_cards, nobles = load_tables()
+        base_cards, base_nobles = load_tables()
         tbl = base_cards if cards is None else np.ascontiguousarray(np.asarray(cards, np.int32))
         if tbl.shape != (90, 8):
             raise ValueError("card table must be int32 [90, 8]")
+        ntbl = base_nobles if nobles is None else np.ascontiguousarray(np.asarray(nobles, np.int32))
+        if ntbl.shape != (10, 6):
+            raise ValueError("noble table must be int32 [10, 6]")
         ctx = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            check(self.lib, self.lib.spl_ctx_create(self.device.index, tbl.ctypes.data, nobles.ctypes.data,
+            check(self.lib, self.lib.spl_ctx_create(self.device.index, tbl.ctypes.data, ntbl.ctypes.data,
                                                     ctypes.byref(ctx)))
         self.ctx = ctx
         # the context's fault word (host-mapped; the kernels write a faulting launch's serial there)
         self._fault_word = ctypes.c_uint64.from_address(self.lib.spl_ctx_fault_word(ctx))
         self.custom_cards = None if cards is None else tbl.copy()
+        self.custom_nobles = None if nobles is None else ntbl.copy()
         refill_period, refill_fused, pipeline, delegation, partner_lead = self._settings
         num_players = self.P
         if refill_period is None:
@@ -134,17 +140,18 @@ class Engine:
         if self._step_tail is not None:
             check(self.lib, self.lib.spl_ctx_set_step_tail(self.ctx, int(self._step_tail)))
 
-    def set_card_table(self, cards=None):
-        """Evaluate the tables from now on with card table `cards` (int32 [90, 8]; None = canonical):
-        a new context over the same arena (the table state does not depend on the context)."""
-        same = (cards is None and self.custom_cards is None) or (
-            cards is not None and self.custom_cards is not None and np.array_equal(cards, self.custom_cards))
-        if same:
+    def set_card_table(self, cards=None, nobles=None):
+        """Evaluate the tables from now on with card table `cards` (int32 [90, 8]) and noble table
+        `nobles` (int32 [10, 6]; None = canonical for either): a new context over the same arena (the
+        table state does not depend on the context)."""
+        def same(new, cur):
+            return (new is None and cur is None) or (new is not None and cur is not None and np.array_equal(new, cur))
+        if same(cards, self.custom_cards) and same(nobles, self.custom_nobles):
             return
         self.torch.cuda.synchronize(self.device)
         old = self.ctx
         self._fault_carry = self.faults()
-        self._create_ctx(cards)
+        self._create_ctx(cards, nobles)
         self.lib.spl_ctx_destroy(old)
 
     # ------------------------------------------------------------------------------------

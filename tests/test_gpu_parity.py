@@ -60,12 +60,18 @@ def test_reset_deals(orc, P):
         assert canon(table_to_view(recs[t])) == canon(vec.table(t)), t
 
 
-def run_parity(orc, P, n, plies, refill_period, seed, device_policy, check_state_every=50):
+def run_parity(orc, P, n, plies, refill_period, seed, device_policy, check_state_every=50, cards=None, nobles=None,
+               watch=None, host_policy=None):
+    """cards / nobles: an edited table pair for the engine (the caller has set the same pair in the oracle
+    library, tests/edited_tables.py oracle_tables).  watch(vec) returns an object whose update(ref) sees
+    every ply's oracle outputs.  host_policy(mask_u64, seed, ply): the device policy restated on the host;
+    the fused policy's next action is then compared with it on the oracle's mask."""
     import torch
-    e = engine(n, P, refill_period=refill_period)
+    e = engine(n, P, refill_period=refill_period, cards=cards, nobles=nobles)
     seeds = [seed + i for i in range(n)]
     e.reset(seeds=seeds)
     vec = OracleVec(orc, n, P, seeds)
+    seen = watch(vec) if watch else None
     rs = np.random.default_rng(seed)
     next_actions = torch.zeros(n, dtype=torch.int32, device=e.device)
     e.sample_uniform(out=next_actions, seed=seed, ply=0)
@@ -95,6 +101,11 @@ def run_parity(orc, P, n, plies, refill_period, seed, device_policy, check_state
         if len(rows):
             np.testing.assert_array_equal(e.final_obs.cpu().numpy()[rows], ref["final_obs"][rows],
                                           err_msg=f"final obs ply {k}")
+        if seen is not None:
+            seen.update(ref)
+        if host_policy is not None:
+            np.testing.assert_array_equal(next_actions.cpu().numpy(), host_policy(ref["mask"], seed, k + 1),
+                                          err_msg=f"next action ply {k}")
         if check_state_every and (k % check_state_every == check_state_every - 1):
             recs = e.download()
             for t in range(0, n, max(1, n // 128)):

@@ -46,6 +46,57 @@ def test_abi_host_side_errors():
     assert lib.spl_step(None, ctypes.byref(arena), None, None) == -1
 
 
+def _ctx_create(cards, nobles):
+    """spl_ctx_create's return code and message for a table pair; a context it made is destroyed."""
+    from splendor_gym import _native
+    lib = _native.load_library()
+    out = ctypes.c_void_p()
+    c, n = np.ascontiguousarray(cards, np.int32), np.ascontiguousarray(nobles, np.int32)
+    rc = lib.spl_ctx_create(0, c.ctypes.data, n.ctypes.data, ctypes.byref(out))
+    msg = lib.spl_last_error().decode()
+    if rc == 0:
+        lib.spl_ctx_destroy(out)
+    return rc, msg
+
+
+def test_ctx_create_refuses_noble_points_outside_a_byte():
+    """Noble points outside 0..255 are an argument error like every other field (they used to be cut to
+    a byte silently), reported before any device work."""
+    from splendor_gym.engine.state import load_tables
+    cards, nobles = load_tables()
+    for bad in (-1, 256, 1000):
+        nb = np.array(nobles, np.int32).copy()
+        nb[7, 5] = bad
+        rc, msg = _ctx_create(cards, nb)
+        assert rc == -1 and "noble points" in msg, (bad, rc, msg)
+
+
+def test_ctx_create_refuses_points_that_overflow_the_prestige_byte():
+    """A player enters a move with at most 14 prestige and gains one card and one noble in it: a table pair
+    with 14 + max card points + max noble points > 255 is SPL_E_RANGE (the packed prestige byte would
+    wrap), at 255 exactly it is accepted — on a host without a GPU the call then gets as far as the device
+    (SPL_E_HIP), never a range or argument error."""
+    from splendor_gym.engine.state import load_tables
+    cards, nobles = load_tables()
+    cd, nb = np.array(cards, np.int32).copy(), np.array(nobles, np.int32).copy()
+    cd[41, 2], nb[3, 5] = 141, 100  # 14 + 141 + 100 = 255
+    rc, msg = _ctx_create(cd, nb)
+    assert rc in (0, -2), (rc, msg)
+    cd[88, 2] = 142                 # 256
+    rc, msg = _ctx_create(cd, nb)
+    assert rc == -3 and "prestige byte" in msg, (rc, msg)
+    cd[88, 2], nb[9, 5] = 141, 101  # 256 through the nobles
+    rc, msg = _ctx_create(cd, nb)
+    assert rc == -3 and "prestige byte" in msg, (rc, msg)
+    cd[:, 2], nb[:, 5] = 0, 241     # 255 with pointless cards
+    assert _ctx_create(cd, nb)[0] in (0, -2)
+    cd[0, 2] = 255                  # the card field's own limit still holds on its own
+    nb[:, 5] = 0
+    assert _ctx_create(cd, nb)[0] == -3
+    cd[0, 2] = 241
+    assert _ctx_create(cd, nb)[0] in (0, -2)
+
+
 def test_policy_abi_host_side_errors():
     """spl_policy_* argument checks (include/splendor_policy.h) run before any device work."""
     from splendor_gym import _native
