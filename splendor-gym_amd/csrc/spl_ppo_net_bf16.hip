@@ -1,7 +1,7 @@
 // spl_ppo_net_bf16.hip — spl_ppo_net_forward_bf16 and spl_ppo_net_backward_bf16 (include/splendor_ppo.h):
 // the passes of spl_ppo_net_tiled.hip with bf16 operands on v_mfma_f32_32x32x16_bf16, float32 accumulation.
-// Same launches (forward: layer 1, layer 2, the output layers; backward: dZ2, dZ1, the sums over rows,
-// k_net_reduce unchanged), same buffers, same treatment of bad rows; NOT the same bytes as the f32 pairs.
+// Same launches, same buffers, same treatment of bad rows (all of it spl_ppo_net_tile.h's, shared with the f32
+// source); NOT the same bytes as the f32 pairs.  Here are the bf16 stages and the matrix-instruction loops.
 //
 // The arithmetic (the header's contract): both operands of every matrix-instruction product are rounded from
 // float32 to bf16, to nearest even, as they are staged into LDS (v_cvt_pk_bf16_f32), so LDS holds bf16 and a
@@ -17,25 +17,18 @@
 // operands of the sums over rows, whose k is the row) is transposed while it is staged: a thread loads one
 // column down k, coalesced across threads, and writes its k-run packed.  Rows are 64 bf16 + 8 of pad = 144 B:
 // the 16 lanes of a ds_read_b128 group then fall on 16 different 16-byte slots of the 256-byte bank row.
-// C/D is the f32 form's: D[i = (q & 3) + 8 (q >> 2) + 4 h][j = r] in register q.
-#include "spl_ppo_net_common.h"
+#include "spl_ppo_net_tile.h"
 
 namespace spln {
-namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kTileRows = SPL_PPO_NET_TILE_ROWS;  // rows of a workgroup of the forward and dZ launches
 constexpr int kStage = 64;                        // k of one stage
 constexpr int kLdb = kStage + 8;                  // row stride of an LDS image, in bf16
 constexpr int kHiPos = kIn;                       // the pad position that carries 256 * byte 297
 constexpr int kHiCol = 295;                       // the column it belongs to
-static_assert(kTileRows == 64, "a workgroup's four waves cover 64 rows as 2 x 2 or 1 x 1 tiles of 32 x 32");
 static_assert(kIn == 297 && SPL_PPO_OBS_U8 == 300, "byte 297 is the dword at 296's second byte");
-
-__device__ __forceinline__ int d_row(int q, int h) { return (q & 3) + 8 * (q >> 2) + 4 * h; }
 
 __device__ __forceinline__ bf16x4 pack4(const float *x) {
     bf16x4 v;
@@ -58,79 +51,10 @@ __device__ __forceinline__ uint32_t input_at(uint32_t w, int k) {
     return k < kIn ? b : k == kHiPos ? b << 8 : 0u;
 }
 
-// ---------------------------------------------------------------------------------------------
-// out = epilogue(C0 + A W): forward layers and the two dZ products
-// ---------------------------------------------------------------------------------------------
-struct Gemm {
-    int B;
-    int64_t total;
-    const int64_t *idx;
-    const uint8_t *obs;
-    const float *a[2];     // the rows' operand where it is floats: [B][256], or dOut
-    const float *w[2];     // the weight
-    const float *bias[2];  // forward: where the sums start
-    const float *h[2];     // dZ: the activations behind the tanh whose derivative is applied, [B][256]
-    float *out[2];
-    unsigned long long *errors;
-};
-
-enum { F1, F2, F3, Z2, Z1 };
-
-template <int MODE>
-struct Shape {
-    static constexpr bool kBytes = MODE == F1;                   // A is rebuilt from the store's bytes
-    static constexpr bool kKMajor = MODE == Z2 || MODE == Z1;    // W is [k][unit]; otherwise [unit][k]
-    static constexpr int kK = MODE == F1 ? kIn : MODE == Z2 ? kA : kH;
-    static constexpr int kKp = (kK + kStage - 1) / kStage * kStage;  // whole stages: 320, 256, 64
-    static constexpr int kUnits = MODE == F3 ? kA : kH;          // live units
-    static constexpr int kNw = MODE == F3 ? 64 : kH;             // units of a workgroup
-    static constexpr int kTm = MODE == F3 ? 1 : 2, kTn = kTm;    // a wave's tiles
-    static constexpr bool kNeedOk = MODE == F1 || MODE == Z2;    // bad rows are zeros in A
-    static constexpr int kWRegs = kNw * kStage / kBlock;         // a thread's elements of a weight stage
-    static constexpr bool kVec = kK % 4 == 0;                    // rows of A and of a [unit][k] W are 16-byte aligned
-};
-
-// The critic's output layer: row b's value = b3 + SUM_k H2[b][k] w3[k], k ascending, a thread a row; float32.
-__device__ __forceinline__ void value_rows(const Gemm &g, int64_t b0) {
-    const int t = threadIdx.x;
-    if (t >= kTileRows) return;
-    const int64_t b = b0 + t, bc = b < g.B ? b : (int64_t)g.B - 1;
-    const int64_t pos = g.idx[bc];
-    const float4 *hrow = reinterpret_cast<const float4 *>(g.a[1] + bc * kH);
-    const float4 *w = reinterpret_cast<const float4 *>(g.w[1]);
-    float y = g.bias[1][0];
-#pragma unroll 16
-    for (int k = 0; k < kH / 4; ++k) {
-        const float4 c = w[k], x = hrow[k];
-        y = __builtin_fmaf(x.x, c.x, y);
-        y = __builtin_fmaf(x.y, c.y, y);
-        y = __builtin_fmaf(x.z, c.z, y);
-        y = __builtin_fmaf(x.w, c.w, y);
-    }
-    if (b < g.B) g.out[1][b] = (pos >= 0 && pos < g.total) ? y : 0.f;
-}
-
-// The critic's dZ2: one product a row and unit, dvalue * w3[t], times 1 - H2^2; thread t the unit; float32.
-__device__ __forceinline__ void dz2_critic_rows(const Gemm &g, int64_t b0) {
-    const int t = threadIdx.x;
-    const float w = g.w[1][t];
-#pragma unroll 8
-    for (int r = 0; r < kTileRows; ++r) {
-        const int64_t b = b0 + r, bc = b < g.B ? b : (int64_t)g.B - 1;  // uniform
-        const int64_t pos = g.idx[bc];
-        const float dv = g.a[1][bc], hh = g.h[1][bc * kH + t];
-        const float d = (pos >= 0 && pos < g.total) ? dv : 0.f;
-        const float z = __builtin_fmaf(d, w, 0.f) * __builtin_fmaf(-hh, hh, 1.f);
-        if (b < g.B) g.out[1][b * kH + t] = z;
-    }
-}
-
-}  // namespace
-
 // grid (row tiles, 2): blockIdx.y 0 the actor, 1 the critic
 template <int MODE>
 __global__ __launch_bounds__(kBlock) void k_bf16_gemm(Gemm g) {
-    using S = Shape<MODE>;
+    using S = Shape<MODE, kStage>;
     const int t = threadIdx.x, net = blockIdx.y;
     const int64_t b0 = (int64_t)blockIdx.x * kTileRows;
     if constexpr (MODE == F3 || MODE == Z2) {
@@ -258,18 +182,7 @@ __global__ __launch_bounds__(kBlock) void k_bf16_gemm(Gemm g) {
     fetch(0);
 
     f32x16 acc[S::kTm][S::kTn];
-#pragma unroll
-    for (int j = 0; j < S::kTn; ++j) {
-        float c0 = 0.f;
-        if constexpr (MODE == F1 || MODE == F2 || MODE == F3) {
-            const int u = u0 + 32 * j + r;
-            c0 = g.bias[net][u < S::kUnits ? u : S::kUnits - 1];
-        }
-#pragma unroll
-        for (int i = 0; i < S::kTm; ++i)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[i][j][q] = c0;
-    }
+    acc_start<MODE>(g, net, u0, r, acc);
 
     for (int k0 = 0; k0 < S::kKp; k0 += kStage) {
         __syncthreads();  // the stage's readers are done
@@ -292,56 +205,15 @@ __global__ __launch_bounds__(kBlock) void k_bf16_gemm(Gemm g) {
         }
     }
 
-    // epilogue: register q of tile (i, j) is row rt0 + 32 i + d_row(q, h), unit u0 + 32 j + r
-#pragma unroll
-    for (int i = 0; i < S::kTm; ++i) {
-        // dZ: a tile's activations are all loaded before its first store (the planes may be one allocation, so
-        // a load behind a store would wait for it: 32 round trips in a row)
-        float hh[16][S::kTn];
-        if constexpr (MODE == Z2 || MODE == Z1) {
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int64_t b = b0 + rt0 + 32 * i + d_row(q, h);
-                const int64_t bc = b < g.B ? b : (int64_t)g.B - 1;
-#pragma unroll
-                for (int j = 0; j < S::kTn; ++j) hh[q][j] = g.h[net][bc * kH + u0 + 32 * j + r];
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int64_t b = b0 + rt0 + 32 * i + d_row(q, h);
-            const int64_t bc = b < g.B ? b : (int64_t)g.B - 1;
-            bool ok = true;
-            if constexpr (MODE == F3) {
-                const int64_t pos = g.idx[bc];
-                ok = pos >= 0 && pos < g.total;
-            }
-#pragma unroll
-            for (int j = 0; j < S::kTn; ++j) {
-                const int u = u0 + 32 * j + r;
-                const float y = acc[i][j][q];
-                if constexpr (MODE == F1 || MODE == F2) {
-                    if (b < g.B) g.out[net][b * kH + u] = tanh_acc(y);
-                } else if constexpr (MODE == F3) {
-                    if (b < g.B && u < kA) g.out[0][b * kA + u] = ok ? y : 0.f;
-                } else {
-                    if (b < g.B) g.out[net][b * kH + u] = y * __builtin_fmaf(-hh[q][j], hh[q][j], 1.f);
-                }
-            }
-        }
-    }
+    tile_store<MODE, true>(g, net, b0, rt0, u0, r, h, acc);
 }
 
 // ---------------------------------------------------------------------------------------------
 // the sums over rows: dW and db of every layer, per partial
 // ---------------------------------------------------------------------------------------------
-// A workgroup sums one block of one dW over the chunks p, p + parts, ... of its partial, 64 rows a stage
-// (zeros past a chunk's end), rows the MFMA's k.  Both operands lie [row][column] in memory and [column][row]
-// in LDS.  The `wide` one has 256 columns, 64 a wave; the `narrow` one 64, which every wave reads:
-//   layer 1: dW1[m][n0 .. n0 + 63]: wide dZ1 (m), narrow X's positions (n), 5 blocks; position 297 is column
-//            295's second half and is added to it in the epilogue
-//   layer 2: dW2[m][n0 .. n0 + 63]: wide dZ2 (m), narrow H1's columns (n), 4 blocks
-//   layer 3: dW3[m < 45 | 1][n]:    wide H2 (n), narrow dOut (m), 1 block
+// The stages are 64 rows; both operands lie [row][column] in memory and [column][row] in LDS (the blocks:
+// spl_ppo_net_tile.h).  In layer 1 the narrow operand's columns are X's positions: position 297 is column 295's
+// second half and is added to it in the epilogue.
 // The bias gradient, the column against ones, is a float32 sum of the unrounded values down the same rows on
 // the VALU: by the thread that stages the column (layers 1 and 2), or by the four threads that stage a
 // quarter of the stage's rows each, added in order at the end (layer 3).
@@ -349,9 +221,7 @@ __global__ __launch_bounds__(kBlock) void k_bf16_gemm(Gemm g) {
 // A wave stages 16 rows of the narrow operand, a lane a column, so a row's position is the same for the whole
 // wave: the sixteen are read by one load, a row a lane, ahead of the first byte that depends on one, and
 // broadcast from their lanes.  No load sits behind a per-lane branch.
-constexpr int kDwBlocks = 5 + 4 + 1;  // a network's
-constexpr int kNarrow = 64;
-constexpr int kDwStage = kStage;      // rows of a stage
+constexpr int kDwStage = kStage;  // rows of a stage
 static_assert(kChunkRows % kDwStage == 0, "a chunk is a whole number of stages");
 
 template <int LAYER>
@@ -417,10 +287,6 @@ __device__ __forceinline__ void dw_block(const Bwd &g, const int net, const int 
             nn[i] = keep ? x : 0.f;
         }
     };
-    auto end_of = [&](int c) {
-        const int64_t e = (int64_t)(c + 1) * kChunkRows;
-        return e < g.B ? e : (int64_t)g.B;
-    };
 
     f32x16 acc[2][2];
 #pragma unroll
@@ -440,7 +306,7 @@ __device__ __forceinline__ void dw_block(const Bwd &g, const int net, const int 
     int c = part;
     int64_t s0 = (int64_t)c * kChunkRows;
     bool more = c < g.chunks;
-    if (more) fetch(s0, end_of(c));
+    if (more) fetch(s0, end_of(g, c));
     while (more) {
         __syncthreads();
 #pragma unroll
@@ -455,13 +321,9 @@ __device__ __forceinline__ void dw_block(const Bwd &g, const int net, const int 
             for (int i = 0; i < 16; ++i) bsum += nn[i];
         }
         __syncthreads();
-        s0 += kDwStage;
-        if (s0 >= end_of(c)) {
-            c += g.parts;
-            s0 = (int64_t)c * kChunkRows;
-        }
+        next_stage(g, kDwStage, c, s0);
         more = c < g.chunks;
-        if (more) fetch(s0, end_of(c));
+        if (more) fetch(s0, end_of(g, c));
 #pragma unroll
         for (int s = 0; s < kDwStage / 16; ++s) {
             bf16x8 av[2], bv[2];
@@ -477,9 +339,7 @@ __device__ __forceinline__ void dw_block(const Bwd &g, const int net, const int 
         }
     }
 
-    const int nc = LAYER == 1 ? kC1 : kC2;
-    const int m_live = LAYER == 3 ? n3 : kH;
-    float *out = g.partial + (int64_t)part * kPartFloats + net * kActorFloats + (LAYER == 1 ? 0 : LAYER == 2 ? kOff2 : kOff3);
+    const DwOut o = dw_out(g, LAYER, net, part);
     if (LAYER == 1 && n0 + kNarrow > kHiPos) {  // uniform: position 297 (lane r + 2 of the same half) into column 295
         static_assert(kHiCol / 32 == kHiPos / 32 && kHiPos - kHiCol == 2, "both in one tile, two lanes apart");
         const int j = (kHiCol - 4 * kNarrow) / 32;
@@ -491,24 +351,15 @@ __device__ __forceinline__ void dw_block(const Bwd &g, const int net, const int 
                 if (n0 + 32 * j + r == kHiCol) acc[i][j][q] += hi;
             }
     }
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int m = (LAYER == 3 ? 0 : 64 * wave) + 32 * i + d_row(q, h);
-                const int n = (LAYER == 3 ? 64 * wave : n0) + 32 * j + r;
-                if (m < m_live && n < nc - 1) out[m * nc + n] = acc[i][j][q];
-            }
+    dw_store(LAYER, o, n0, wave, r, h, acc);
     if (wide_bias) {
-        out[t * nc + nc - 1] = bsum;
+        o.out[t * o.nc + o.nc - 1] = bsum;
     } else if constexpr (LAYER == 3) {  // the four quarters of a stage's rows, in order
         __syncthreads();
         float *const q4 = reinterpret_cast<float *>(lds);
         q4[nq * kNarrow + ncol] = bsum;
         __syncthreads();
-        if (t < m_live) out[t * nc + nc - 1] = ((q4[t] + q4[kNarrow + t]) + q4[2 * kNarrow + t]) + q4[3 * kNarrow + t];
+        if (t < o.m_live) o.out[t * o.nc + o.nc - 1] = ((q4[t] + q4[kNarrow + t]) + q4[2 * kNarrow + t]) + q4[3 * kNarrow + t];
     }
 }
 
@@ -534,41 +385,11 @@ using namespace spln;
 extern "C" {
 
 int spl_ppo_net_forward_bf16(int32_t B, const spl_ppo_net_fwd_t *a, void *stream) {
-    Fwd f;
-    if (const int e = fwd_args(B, a, f)) return e;
-    const int64_t slot = (int64_t)B * kH;  // act: [network][layer][B][256]
-    Gemm g{};
-    g.B = B, g.total = f.total, g.idx = f.idx, g.obs = f.obs, g.errors = f.errors;
-    const hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)((B + kTileRows - 1) / kTileRows), 2), block(kBlock);
-    for (int n = 0; n < 2; ++n) g.a[n] = nullptr, g.w[n] = f.net[n].w1, g.bias[n] = f.net[n].b1, g.out[n] = f.act + (2 * n) * slot;
-    hipLaunchKernelGGL(k_bf16_gemm<F1>, grid, block, 0, s, g);
-    for (int n = 0; n < 2; ++n)
-        g.a[n] = f.act + (2 * n) * slot, g.w[n] = f.net[n].w2, g.bias[n] = f.net[n].b2, g.out[n] = f.act + (2 * n + 1) * slot;
-    hipLaunchKernelGGL(k_bf16_gemm<F2>, grid, block, 0, s, g);
-    for (int n = 0; n < 2; ++n) g.a[n] = f.act + (2 * n + 1) * slot, g.w[n] = f.net[n].w3, g.bias[n] = f.net[n].b3;
-    g.out[0] = f.logits, g.out[1] = f.value;
-    hipLaunchKernelGGL(k_bf16_gemm<F3>, grid, block, 0, s, g);
-    return spl_launched("k_bf16_gemm (forward)");
+    return forward_tiles(B, a, stream, k_bf16_gemm<F1>, k_bf16_gemm<F2>, k_bf16_gemm<F3>, "k_bf16_gemm (forward)");
 }
 
 int spl_ppo_net_backward_bf16(int32_t B, const spl_ppo_net_bwd_t *a, void *stream) {
-    Bwd b;
-    if (const int e = bwd_args(B, a, b)) return e;
-    const int64_t slot = (int64_t)B * kH;  // act: [network][layer][B][256]; dz: [network][dZ2, dZ1][B][256]
-    Gemm g{};
-    g.B = B, g.total = b.total, g.idx = b.idx, g.obs = b.obs;
-    const hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)((B + kTileRows - 1) / kTileRows), 2), block(kBlock);
-    for (int n = 0; n < 2; ++n)
-        g.a[n] = b.dout[n], g.w[n] = b.w3[n], g.h[n] = b.act + (2 * n + 1) * slot, g.out[n] = b.dz + (2 * n) * slot;
-    hipLaunchKernelGGL(k_bf16_gemm<Z2>, grid, block, 0, s, g);
-    for (int n = 0; n < 2; ++n)
-        g.a[n] = b.dz + (2 * n) * slot, g.w[n] = b.w2[n], g.h[n] = b.act + (2 * n) * slot, g.out[n] = b.dz + (2 * n + 1) * slot;
-    hipLaunchKernelGGL(k_bf16_gemm<Z1>, grid, block, 0, s, g);
-    hipLaunchKernelGGL(k_bf16_dw, dim3(2 * kDwBlocks, b.parts), block, 0, s, b);
-    launch_net_reduce(b, s);
-    return spl_launched("k_bf16_gemm (backward)");
+    return backward_tiles(B, a, stream, k_bf16_gemm<Z2>, k_bf16_gemm<Z1>, k_bf16_dw, "k_bf16_gemm (backward)");
 }
 
 }  // extern "C"

@@ -3,6 +3,7 @@
 // the same tiles with bf16 operands): the sizes, the layout of the partial sums in `scratch`, tanh_acc, the
 // kernels' argument blocks and the host-side checks that fill them.  The two f32 sources give the same bytes,
 // so everything that fixes a summation order is here; the bf16 source keeps the split of the sums over rows.
+// What only the two tiled sources share, the tile apart from its operand format, is spl_ppo_net_tile.h.
 #pragma once
 #include "../../include/splendor_ppo.h"
 #include "spl_common.h"

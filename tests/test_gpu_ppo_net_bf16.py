@@ -23,6 +23,7 @@ checkpoint on the collected store's rows): logits 5.38e-4, value 4.20e-3, actor 
 b2 2.75e-3, w3 2.19e-3, critic w1 2.74e-3, b1 2.58e-3, w2 2.41e-3, b2 8.55e-4, w3 2.31e-3; the kernel's were
 0.999 to 1.001 of them."""
 import copy
+import functools
 
 import numpy as np
 import pytest
@@ -32,10 +33,9 @@ from bf16_nets import product, to_bf16, ulp32
 from crafted_nets import forward64
 from test_gpu_ppo_adam import EPS, LR, bits, finite_figures, run_cli
 from test_gpu_ppo_loss import DEV, collected, trained  # noqa: F401  (collected: a module fixture)
-from test_gpu_ppo_net import (CRAFTED, K, P, SENTINEL, T, agents, gaps_untouched, gradients, in_arena, make_idx,  # noqa: F401
-                              minibatch, rows_of, store)
-from test_gpu_ppo_net_tiled import Counting, every_word_written
-from test_ppo_net_host import FIELDS, NA, NETS, net_oracle, params_of, tensors_of
+from test_gpu_ppo_net import CRAFTED, K, P, T, agents, gradients, make_idx, minibatch, rows_of, store  # noqa: F401
+from test_gpu_ppo_net_tiled import Counting, every_word_written, passes as net_passes
+from test_ppo_net_host import FIELDS, NA, NETS, net_oracle, params_of
 
 pytestmark = pytest.mark.gpu
 
@@ -46,38 +46,8 @@ SIZES = (1, 63, 64, 65, 129, 257, 4097, 4225)
 N_COMBINE = 32 + 1 + 4
 
 
-def passes(agent, store, idx, dlogits, dvalue, fill=SENTINEL, tiled=False):
-    """DeviceNets(operands="bf16").forward and backward with every output pre-filled with `fill`.  Returns the
-    int32 views of logits, value, act, scratch and the gradients' arena (test_gpu_ppo_net_tiled.passes' layout),
-    the float32 host copies under "f", and by how much store.errors rose in each of the two calls."""
-    import torch
-    from splendor_gym.ppo import DeviceNets
-    a, arena, views = in_arena(agent)
-    arena.fill_(fill)
-    nets = DeviceNets(a, tiled=tiled, operands="bf16")
-    assert all(p.grad.data_ptr() == v.data_ptr() for p, v in zip(tensors_of(a), views))  # taken in place
-    B = len(idx)
-    bufs = nets._buffers(B)
-    for name in ("logits", "value", "act", "scratch"):
-        bufs[name].fill_(fill)
-    d_idx = torch.from_numpy(idx).to(DEV)
-    e0 = int(store.errors.item())
-    logits, value = nets.forward(store, d_idx)
-    e1 = int(store.errors.item())
-    nets.backward(store, d_idx, torch.from_numpy(dlogits).to(DEV), torch.from_numpy(dvalue).to(DEV))
-    torch.cuda.synchronize()
-    e2 = int(store.errors.item())
-    if fill == SENTINEL:
-        assert gaps_untouched(arena, views)
-    dev = {"logits": logits, "value": value, "act": bufs["act"], "scratch": bufs["scratch"], "arena": arena}
-    out = {k: v.reshape(-1).view(torch.int32).clone() for k, v in dev.items()}
-    out["views"] = [v.reshape(-1).view(torch.int32).clone() for v in views]
-    out["errors"] = (e1 - e0, e2 - e1)
-    out["f"] = {"logits": logits.cpu().numpy().copy(), "value": value.cpu().numpy().copy(),
-                "act": bufs["act"].cpu().numpy()[:4 * B * H].reshape(2, 2, B, H).copy(),
-                "dz": bufs["scratch"].cpu().numpy()[:4 * B * H].reshape(2, 2, B, H).copy(),
-                "grads": {net: [v.cpu().numpy().copy() for v in views[6 * i:6 * i + 6]] for i, net in enumerate(NETS)}}
-    return out
+# test_gpu_ppo_net_tiled.passes on DeviceNets(operands="bf16"), with the float32 host copies under "f"
+passes = functools.partial(net_passes, floats=True, operands="bf16")
 
 
 def params32(agent):

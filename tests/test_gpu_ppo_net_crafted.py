@@ -55,8 +55,8 @@ def both(label, agent, store):
     agent = agent.to(DEV)
     idx = minibatch()
     dlogits, dvalue = gradients(5, B)
-    want = passes(agent, store, idx, dlogits, dvalue, False, False)
-    got = passes(agent, store, idx, dlogits, dvalue, True, True)
+    want = passes(agent, store, idx, dlogits, dvalue, tiled=False)
+    got = passes(agent, store, idx, dlogits, dvalue, tiled=True)
     same_bytes(label, got, want)
     assert want["errors"] == (len(BAD), 0)
     f = lambda w, shape: w.view(torch.float32).double().cpu().numpy().reshape(shape)

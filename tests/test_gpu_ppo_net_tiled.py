@@ -13,7 +13,7 @@ from test_gpu_ppo_adam import EPS, LR, bits, run_cli, run_update
 from test_gpu_ppo_loss import DEV, collected  # noqa: F401  (collected: a module fixture)
 from test_gpu_ppo_net import (COEF, CRAFTED, P, SENTINEL, agents, gaps_untouched, gradients, in_arena, make_idx,  # noqa: F401
                               minibatch, store)
-from test_ppo_net_host import NA, tensors_of
+from test_ppo_net_host import NA, NETS, tensors_of
 
 pytestmark = pytest.mark.gpu
 
@@ -26,15 +26,16 @@ def tile_rows():
     return _native.PPO_NET_TILE_ROWS
 
 
-def passes(agent, store, idx, dlogits, dvalue, forward_tiled, backward_tiled, fill=SENTINEL):
-    """DeviceNets.forward and backward on the chosen paths with every output pre-filled with `fill`.  Returns the
-    int32 views of logits, value, the whole of act, the whole of scratch and the gradients' arena, and by how
-    much store.errors rose in each of the two calls."""
+def passes(agent, store, idx, dlogits, dvalue, *, fill=SENTINEL, backward_tiled=None, floats=False, **nets_kw):
+    """DeviceNets(agent, **nets_kw).forward and backward with every output pre-filled with `fill`; `backward_tiled`
+    sets nets.tiled between the two calls.  Returns the int32 views of logits, value, the whole of act, the whole
+    of scratch and the gradients' arena, by how much store.errors rose in each of the two calls, and with
+    `floats` the float32 host copies under "f"."""
     import torch
     from splendor_gym.ppo import DeviceNets
     a, arena, views = in_arena(agent)
     arena.fill_(fill)
-    nets = DeviceNets(a, tiled=forward_tiled)
+    nets = DeviceNets(a, **nets_kw)
     assert all(p.grad.data_ptr() == v.data_ptr() for p, v in zip(tensors_of(a), views))  # taken in place
     B = len(idx)
     bufs = nets._buffers(B)
@@ -44,16 +45,22 @@ def passes(agent, store, idx, dlogits, dvalue, forward_tiled, backward_tiled, fi
     e0 = int(store.errors.item())
     logits, value = nets.forward(store, d_idx)
     e1 = int(store.errors.item())
-    nets.tiled = backward_tiled  # the buffers are per B and shared between the two paths
+    if backward_tiled is not None:
+        nets.tiled = backward_tiled  # the buffers are per B and shared between the two paths
     nets.backward(store, d_idx, torch.from_numpy(dlogits).to(DEV), torch.from_numpy(dvalue).to(DEV))
     torch.cuda.synchronize()
     e2 = int(store.errors.item())
     if fill == SENTINEL:
         assert gaps_untouched(arena, views)
-    out = {"logits": logits, "value": value, "act": bufs["act"], "scratch": bufs["scratch"], "arena": arena}
-    out = {k: v.reshape(-1).view(torch.int32).clone() for k, v in out.items()}
+    dev = {"logits": logits, "value": value, "act": bufs["act"], "scratch": bufs["scratch"], "arena": arena}
+    out = {k: v.reshape(-1).view(torch.int32).clone() for k, v in dev.items()}
     out["views"] = [v.reshape(-1).view(torch.int32).clone() for v in views]
     out["errors"] = (e1 - e0, e2 - e1)
+    if floats:
+        out["f"] = {"logits": logits.cpu().numpy().copy(), "value": value.cpu().numpy().copy(),
+                    "act": bufs["act"].cpu().numpy()[:4 * B * H].reshape(2, 2, B, H).copy(),
+                    "dz": bufs["scratch"].cpu().numpy()[:4 * B * H].reshape(2, 2, B, H).copy(),
+                    "grads": {net: [v.cpu().numpy().copy() for v in views[6 * i:6 * i + 6]] for i, net in enumerate(NETS)}}
     return out
 
 
@@ -90,7 +97,7 @@ def existing(agents, store, kind, B):
     """The existing path's bytes for make_idx(B, B) and gradients(B, B): computed once, shared, never changed."""
     if (kind, B) not in _existing:
         idx = make_idx(B, B)
-        _existing[kind, B] = passes(agents[kind], store, idx, *gradients(B, B), False, False)
+        _existing[kind, B] = passes(agents[kind], store, idx, *gradients(B, B), tiled=False)
     return _existing[kind, B]
 
 
@@ -102,7 +109,7 @@ def test_same_bytes_as_the_existing_path(store, agents, kind, B):
     chunk, of one row) and 4 225 (34 chunks: partial 0 a whole second chunk, partial 1 a ragged one).  Every
     word of every output is written; the gaps between the gradients are not."""
     want = existing(agents, store, kind, B)
-    got = passes(agents[kind], store, make_idx(B, B), *gradients(B, B), True, True)
+    got = passes(agents[kind], store, make_idx(B, B), *gradients(B, B), tiled=True)
     every_word_written(want, B)
     every_word_written(got, B)
     same_bytes(f"tiled {kind} B={B}", got, want)
@@ -114,7 +121,7 @@ def test_either_forward_goes_with_either_backward(store, agents):
     want = existing(agents, store, "trained", B)
     idx, (dlogits, dvalue) = make_idx(B, B), gradients(B, B)
     for forward_tiled, backward_tiled in ((True, False), (False, True)):
-        got = passes(agents["trained"], store, idx, dlogits, dvalue, forward_tiled, backward_tiled)
+        got = passes(agents["trained"], store, idx, dlogits, dvalue, tiled=forward_tiled, backward_tiled=backward_tiled)
         every_word_written(got, B)
         same_bytes(f"forward tiled={forward_tiled} backward tiled={backward_tiled}", got, want)
 
@@ -132,8 +139,8 @@ def test_column_295_and_bad_rows(store, agents):
     idx[[R - 1, R, 2 * R]] = (-1, P, 2 ** 40)
     dlogits, dvalue = gradients(17, B)
     planes = store.obs_u8.clone()
-    want = passes(agents["trained"], store, idx, dlogits, dvalue, False, False)
-    got = passes(agents["trained"], store, idx, dlogits, dvalue, True, True)
+    want = passes(agents["trained"], store, idx, dlogits, dvalue, tiled=False)
+    got = passes(agents["trained"], store, idx, dlogits, dvalue, tiled=True)
     same_bytes("bad rows", got, want)
     assert got["errors"] == (3, 0)
     logits, value = got["logits"].view(B, NA), got["value"]
@@ -160,8 +167,8 @@ def test_overwrite_and_determinism(store, agents):
     idx = make_idx(B, 4)
     idx[10] = -1
     dlogits, dvalue = gradients(4, B)
-    first = passes(agents["fresh"], store, idx, dlogits, dvalue, True, True)
-    dirty = passes(agents["fresh"], store, idx, dlogits, dvalue, True, True, fill=123.0)
+    first = passes(agents["fresh"], store, idx, dlogits, dvalue, tiled=True)
+    dirty = passes(agents["fresh"], store, idx, dlogits, dvalue, tiled=True, fill=123.0)
     for name in ("logits", "value", "act"):
         assert torch.equal(first[name], dirty[name]), name
     assert torch.equal(first["scratch"][:4 * B * H], dirty["scratch"][:4 * B * H])
