@@ -7,6 +7,17 @@
 // move_count, patched separately) and leave the CU as coalesced 16-byte int32x4 stores; masks
 // leave as packed bytes built from per-lane 45-bit words in LDS.
 //
+// This file is the engine's one translation unit (a kernel is launched from the file that defines it).  Its bottom
+// layers are headers, included below in layer order, which is the order their definitions always had; a layer
+// includes only layers below it:
+//   spl_engine_args.h      kernel argument blocks, build switches (SPL_ABL, SPL_CHECK), lane_id
+//   spl_engine_stamps.h    the SPL_STAMPS diagnostics                                  (on args)
+//   spl_engine_base.h      stream limit, defaults, wg_block, LDS blocks, small helpers
+//   spl_engine_rules.h     the rules on a table in registers                           (on args, base)
+// The layers above them are still sections of this file, bottom up: the observation encoder, the deal, one env
+// step, k_rollout, the two-wave kernels' shared part, spl_step's kernels, the hand-offs, the split-wave rollouts,
+// the utility kernels; then the host side.
+//
 // Reference semantics restated here (paths relative to the reference root):
 //   engine/rules.py:40-93 legal_moves, :101-122 _pay_for_card, :125-129 _refill_slot,
 //   :132-147 _grant_noble_if_applicable, :150-193 auto_return_tokens/_enforce_token_limit,
@@ -30,875 +41,12 @@
 #include "spl_rng.h"
 #include "spl_scripted.h"
 
+#include "spl_engine_args.h"
+#include "spl_engine_stamps.h"
+#include "spl_engine_base.h"
+#include "spl_engine_rules.h"
+
 namespace spl {
-
-// ------------------------------------------------------------------------------------------
-// kernel parameter blocks
-// ------------------------------------------------------------------------------------------
-struct KArena {
-    uint32_t *planes;  // [num_words(P)][n] table state
-    uint32_t *pool;    // [PL_COUNT][n] pool deal's board / noble words
-    uint8_t *slots;    // [n][2][128] deck records
-    uint8_t *pcg;      // [n][64] engine-seed streams
-    int n;
-    uint8_t *deleg;    // [n/128][kDelegTasks][num_words(P) x 64] u32 staged state words (rollout-store delegation)
-    uint32_t *dflags;  // [n/128][kDelegFlagWords] its flags
-    uint32_t *legal;   // [2][n] legal-mask cache of the stored state (spl_layout.h)
-};
-
-struct KTables {
-    const uint4 *cards;   // [90] {1,tier,points,oh_w | oh_b..oh_k | cost w,b,g,r | cost k,colour,0,0}
-    const uint2 *nobles;  // [10] {1,req w,b,g | req r,k,points,0}
-    const uint4 *lut;     // [kLutEntries] token-return MT outputs (top 3 bits, 10 per word)
-    uint32_t mtag;        // this context's legal-mask cache tag (bits 0-15: 1..65535) | kTagFreeCard
-};
-// Bit 31 of KTables::mtag: the card table has a card of total cost 0, so a fresh deal may allow a purchase and
-// reset lanes evaluate legal_moves instead of taking kFreshDealMask.  Set at context creation; a kernel argument,
-// so the branch on it is wave-uniform, and it rides in the tag's word, so it costs the kernels no register.
-constexpr uint32_t kTagFreeCard = 1u << 31;
-__device__ __forceinline__ bool has_free_card(const KTables &Tb) { return (Tb.mtag & kTagFreeCard) != 0u; }
-
-struct KStep {
-    const int32_t *actions;
-    int32_t *obs;
-    int8_t *mask;
-    float *reward;
-    uint8_t *terminated;
-    uint8_t *flags;
-    int8_t *winner;
-    int32_t *final_obs;
-    int32_t *next_actions;
-    float *ep_return;
-    uint32_t *ep_count;
-    uint8_t *info;             // nullable: [4][n] info planes + truncated (spl_step)
-    uint8_t *obs_u8;           // nullable: [n][300] compact observation instead of obs (k_step_ws)
-    const uint8_t *gate_terminated, *gate_flags;  // nullable: the dual step's gate (spl_step_args_t)
-    unsigned long long *errors;  // nullable: running count of tables with an error flag (spl_step)
-    const uint64_t *ply_base;  // nullable: device counter added to `ply` (graph replays)
-    uint64_t *fault;           // nullable: the context's host-mapped fault word (spl_ctx_faults)
-    uint64_t fault_tag;        // what a faulting launch writes there (the context's launch serial)
-    uint64_t policy_seed;
-    uint64_t ply;
-    int64_t table0;
-    int autoreset;
-    int policy;
-};
-
-// Ablation switches for profiling builds only (tools/ablate.py); the product build defines none.
-#ifndef SPL_ABL
-#define SPL_ABL 0
-#endif
-// (bits 16, 64, 512 and 2048 belonged to the one-wave step kernel; the others keep the values past profiles quote)
-constexpr int ABL_LEGAL_PRE = 1, ABL_APPLY = 2, ABL_LEGAL_POST = 4, ABL_FINAL = 8, ABL_ENCODE = 32,
-              ABL_MASK_STORE = 128, ABL_SMALL_OUT = 256, ABL_OBS_STORE = 1024,
-              ABL_TOKLIM = 4096, ABL_NOBLE = 8192, ABL_DECK_GATHER = 16384, ABL_LUT_GATHER = 32768;
-__device__ __forceinline__ bool abl(int bit) { return (SPL_ABL & bit) != 0; }
-
-// Bounds-check build (-DSPL_BOUNDS_CHECK; libsplendor_amd_checked.so, tests/test_gpu_bounds_check.py):
-// index and range invariants are tested at run time and violations recorded as bits of
-// g_bounds_flags (an atomic OR: a checked run never faults, it reports).  The product build
-// compiles every check out.
-#ifdef SPL_BOUNDS_CHECK
-__device__ uint32_t g_bounds_flags;
-#define SPL_CHECK(cond, bit)                                              \
-    do {                                                                  \
-        if (!(cond)) atomicOr(&g_bounds_flags, (uint32_t)(bit));          \
-    } while (0)
-#else
-#define SPL_CHECK(cond, bit) \
-    do {                     \
-    } while (0)
-#endif
-enum : uint32_t {
-    BC_TABLE = 1, BC_SLOT = 2, BC_DECK = 4, BC_LUT = 8, BC_SCRATCH = 16, BC_BYTE = 32, BC_ROWS = 64, BC_CARD = 128,
-    BC_SPIN = 256,  // a wave gave up waiting for an LDS hand-off (dealer rollout)
-    BC_BARRIER = 512  // a wave of a multi-team workgroup made another number of s_barriers than 1 + K
-};
-
-__device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63u); }
-// sub-phase stamp hook of step_rules (diagnostic builds pass a stamping one)
-struct NoStamp {
-    __device__ __forceinline__ void operator()(int) const {}
-};
-
-// Phase stamps for the diagnostic build only (-DSPL_STAMPS, tools/stamps.py): lane 0 of every
-// wave records s_memrealtime (100 MHz) at phase boundaries of step_ws.  Never in the product build.
-#ifdef SPL_STAMPS
-__device__ uint64_t *g_stamps;
-#define STAMP(i)                                                                                 \
-    do {                                                                                         \
-        __builtin_amdgcn_sched_barrier(0);                                                       \
-        if ((threadIdx.x & 63) == 0 && g_stamps) g_stamps[((size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 16 + (i)] = __builtin_amdgcn_s_memrealtime(); \
-        __builtin_amdgcn_sched_barrier(0);                                                       \
-    } while (0)
-// a value instead of a time in stamp slot i (e.g. a wave's terminal-row count)
-#define STAMPV(i, v)                                                                             \
-    do {                                                                                         \
-        if ((threadIdx.x & 63) == 0 && g_stamps) g_stamps[((size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 16 + (i)] = (uint64_t)(v); \
-    } while (0)
-// k_rollout keeps its stamps in registers (lane k holds step k's) so that stamping never waits
-// on the stores in flight; they are written to g_rstamps[wave][step][kRStamps] at the end.
-constexpr int kRStamps = 6;
-__device__ uint64_t *g_rstamps;
-#define RSTAMP(i, k)                                                                             \
-    do {                                                                                         \
-        __builtin_amdgcn_sched_barrier(0);                                                       \
-        const uint64_t tt_ = __builtin_amdgcn_s_memrealtime();                                   \
-        rst_lo[i] = lane_id() == (k) ? (int)(uint32_t)tt_ : rst_lo[i];                           \
-        rst_hi[i] = lane_id() == (k) ? (int)(uint32_t)(tt_ >> 32) : rst_hi[i];                   \
-        __builtin_amdgcn_sched_barrier(0);                                                       \
-    } while (0)
-// rollout_ws (k_rollout_store_*, k_rollout_inplace_*): both waves keep kWsStamps stamps per step in registers (lane k = step k, K <= 64),
-// written to g_wsstamps[workgroup][wave][step][kWsStamps] at the end.
-constexpr int kWsStamps = 11;  // 0-3 per step; 4-10 sub-phases of the rules wave
-__device__ uint64_t *g_wsstamps;
-__device__ uint32_t *g_wshwid;  // [workgroup][wave][2]: HW_ID (SIMD, CU, SE) and XCC_ID of each wave
-__device__ uint64_t *g_wsclk;   // [workgroup][4]: s_memtime / s_memrealtime at the rules wave's start and end
-__device__ uint64_t *g_wsend;   // [workgroup][2]: s_memrealtime at the output wave's last step and at its end
-#define WSHWID(sid, wave)                                                                        \
-    do {                                                                                         \
-        if (g_wshwid && lane_id() == 0) {                                                        \
-            g_wshwid[((size_t)(sid) * 2 + (wave)) * 2 + 0] = __builtin_amdgcn_s_getreg((31 << 11) | 4);  \
-            g_wshwid[((size_t)(sid) * 2 + (wave)) * 2 + 1] = __builtin_amdgcn_s_getreg((31 << 11) | 20); \
-        }                                                                                        \
-    } while (0)
-// a rules / output wave's stamps of one launch (rules_wave, output_wave): at(i, k) is stamp i of step k
-struct WsStamps {
-    int rst_lo[kWsStamps] = {0}, rst_hi[kWsStamps] = {0};
-    uint64_t clk0 = 0, rt0 = 0;
-    struct Sub {  // step_rules' sub-phase hook
-        WsStamps &st;
-        int k;
-        __device__ __forceinline__ void operator()(int i) const { st.at(i, k); }
-    };
-    __device__ __forceinline__ void at(int i, int k) { RSTAMP(i, k); }
-    __device__ __forceinline__ Sub sub(int k) { return Sub{*this, k}; }
-    __device__ __forceinline__ void start() {
-        clk0 = __builtin_amdgcn_s_memtime();
-        rt0 = __builtin_amdgcn_s_memrealtime();
-    }
-    // the rules wave's clocks from start() to now -> g_wsclk[sid]
-    __device__ __forceinline__ void flush_clocks(int sid) const {
-        const uint64_t clk1 = __builtin_amdgcn_s_memtime(), rt1 = __builtin_amdgcn_s_memrealtime();
-        if (g_wsclk && lane_id() == 0) {
-            g_wsclk[sid * 4 + 0] = clk0;
-            g_wsclk[sid * 4 + 1] = rt0;
-            g_wsclk[sid * 4 + 2] = clk1;
-            g_wsclk[sid * 4 + 3] = rt1;
-        }
-    }
-    // the per-step stamps -> g_wsstamps[sid][wave]
-    __device__ __forceinline__ void flush(int sid, int wave, int K) const {
-        if (g_wsstamps && lane_id() < K)
-            for (int i = 0; i < kWsStamps; ++i)
-                g_wsstamps[(((size_t)sid * 2 + wave) * 64 + lane_id()) * kWsStamps + i] =
-                    ((uint64_t)(uint32_t)rst_hi[i] << 32) | (uint32_t)rst_lo[i];
-    }
-    // now -> g_wsend[sid][i]; `drained`: once this wave's stores have completed
-    __device__ __forceinline__ void end(int sid, int i, bool drained) const {
-        if (!g_wsend) return;
-        if (drained) __builtin_amdgcn_s_waitcnt(0);
-        if (lane_id() == 0) g_wsend[sid * 2 + i] = __builtin_amdgcn_s_memrealtime();
-    }
-};
-#else
-#define WSHWID(sid, wave) \
-    do {                  \
-    } while (0)
-struct WsStamps {
-    __device__ __forceinline__ void at(int, int) {}
-    __device__ __forceinline__ NoStamp sub(int) { return NoStamp(); }
-    __device__ __forceinline__ void start() {}
-    __device__ __forceinline__ void flush_clocks(int) const {}
-    __device__ __forceinline__ void flush(int, int, int) const {}
-    __device__ __forceinline__ void end(int, int, bool) const {}
-};
-#define STAMP(i) \
-    do {         \
-    } while (0)
-#define STAMPV(i, v) \
-    do {             \
-    } while (0)
-#define RSTAMP(i, k) \
-    do {             \
-    } while (0)
-#endif
-// Outputs a lane takes from the register-only MTStream before a LaneMT continuation takes over
-// (MTStream::kMaxOut; lowered only by the test hook spl_debug_set_stream_limit, so the parity tests
-// can drive every deal and token return through the continuation path).
-__device__ int g_stream_limit = MTStream::kMaxOut;
-
-// Per-lane deal scratch in LDS: an odd number of dwords, so lanes at the same Fisher-Yates
-// position (the common case: lanes decrement their index in step) hit 64 different banks.
-constexpr int kScratchStride = 116;
-// rollout-store delegation period a context starts with (spl_ctx_set_rollout_delegation): off.  Alternating
-// A/B on one box, 12 launches per arm of 128 steps at 65 536 tables: 1999 +- 25 us off vs
-// 1969 +- 34 us every 6th step, a 1.5 % gain (profiles/r03/deleg_ab_r03a.txt) -- under the 2 %
-// that would pay for a cross-XCC hand-off in the headline kernel
-constexpr int kDelegEveryDefault = 0;
-// partner hand-off of the one-workgroup-per-CU rollout stores (six-wave dealer, quad; spl_ctx_set_partner_lead):
-// a team hands a step's rows to its neighbouring-XCC partner when that one is this many steps ahead.
-// A context starts with 0 (off) since round 6's sc0 nt sc1 row stores (kRollCpol): the teams then lag far less
-// and the polls cost more than the hand-off recovers — quad lead 0 / 4 / 8: 1 873-1 898 / 1 909-1 925 /
-// 1 912-1 913 us per launch (another box: lead 0 / 4 1 863-1 873 / 1 892-1 900,
-// profiles/r06/quad_lead_ab_r06ad.txt); six-wave dealer (C4) 1 075-1 078 / 1 081-1 100 / 1 083-1 102
-// (profiles/r06/c4_lead_ab_r06ag.txt).  With nt-only stores lead 4 had paid 2.4 % (headline,
-// profiles/r06/headab_r06d.txt) and ~2 % (C4, profiles/r04/partner_ab_r04u.txt).
-constexpr int kPartnerLeadDefault = 0;
-// Workgroup -> 64-table block, XCD-contiguous.  The dispatcher hands workgroup b to XCD b % 8, so
-// with the identity map every XCD writes every eighth 76 KB chunk of a step's rollout-store block;
-// mapped, XCD x's workgroups own tables [x n/8, (x+1) n/8) and each XCD streams one contiguous eighth
-// of the block (store-only pattern: 880 -> 844-862 us per 64 steps on one box,
-// tools/microbench_hbm_store.hip rows_x).  Only which workgroup steps which tables changes: every
-// table's chain is its own, so results are identical.  A grid that is no multiple of 8 keeps the identity.
-__device__ __forceinline__ int wg_block_of(uint32_t b) {
-    const uint32_t nb = gridDim.x;
-    if (nb & 7u) return (int)b;
-    return (int)((b & 7u) * (nb >> 3) + (b >> 3));
-}
-__device__ __forceinline__ int wg_block() { return wg_block_of(blockIdx.x); }
-// spl_step's int32 rows leave k_step_ws and k_step_wst as `sc1` buffer stores (16: system scope, temporal).
-// k_step_ws (four workgroups per CU): 22.35 -> 20.5 us per step at 65 536 tables against plain stores,
-// `sc0 sc1` the same, `sc0` alone as plain (profiles/r06/step_ws_temporal_policy_r06an.txt); non-temporal
-// rows cost 22.4 -> 23.8 us there (profiles/r06/step_store_policy_ab_r06x.txt), half the block non-temporal
-// 22.2 vs 22.4 (profiles/r06/step_ws_split_policy_r06z.txt), non-temporal rows beside a compact copy neutral
-// (profiles/r06/dual_opp_rows_nt_r06aa.txt).
-// k_step_wst (at most three workgroups per CU): 15.98 -> 15.07 us at 32 768 tables, 20.0 -> 18.2 at 49 152,
-// 12.85 -> 12.82 at 16 384 against sc0 nt sc1 (profiles/r06/step_tail_sc1_ab_r06ap.txt), which itself had
-// beaten plain stores 17.1 -> 16.0 us at 32 768 tables (profiles/r06/step_tail_store_ab_r06y.txt).
-// k_step_wso keeps plain stores (store_obs_block_mid), and so does every spl_step mask block (sc1 there:
-// 20.79 vs 20.62 us at 65 536 tables, equal at 32 768; profiles/r06/step_mask_policy_ab_r06ar.txt).
-constexpr int kStepRowCpol = 16;
-
-constexpr int kMaskStreamWords = 64 * 45 / 32;  // 90
-
-// constant tables staged per workgroup: 16-B obs-ready card records and 8-B noble records
-struct __align__(16) Consts {
-    uint4 cards[90];
-    uint2 nobles[10];
-};
-
-// one wave's output staging
-struct __align__(16) WaveBuf {
-    uint64_t mask[64];
-    uint32_t mbits[96];  // the wave's 64 x 45 mask bits as one stream (store_mask_block)
-    uint8_t rows[64 * kObsDim];   // observation staging; also the deal scratch (64 x 112 B)
-    uint8_t frows[64 * kObsDim];  // terminal observations (k_rollout): stored with the step's other outputs
-};
-struct __align__(16) BlockLDS : Consts, WaveBuf {};
-
-// ------------------------------------------------------------------------------------------
-// small helpers
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t bget(uint32_t w, int k) { return (w >> (8 * k)) & 0xFFu; }
-__device__ __forceinline__ uint32_t bset(uint32_t w, int k, uint32_t v) {
-    return (w & ~(0xFFu << (8 * k))) | ((v & 0xFFu) << (8 * k));
-}
-
-// Launder a value through an empty asm so that a select chain over struct members stays a
-// select of VALUES: otherwise LLVM folds "c ? s.a : s.b" into a load at a selected offset,
-// which pins the whole struct in scratch memory.
-__device__ __forceinline__ uint32_t opaque(uint32_t x) {
-    asm("" : "+v"(x));
-    return x;
-}
-__device__ __forceinline__ int opaque(int x) {
-    asm("" : "+v"(x));
-    return x;
-}
-
-template <int P>
-struct Tab {
-    uint32_t sw[SW_COUNT];
-    uint32_t pw[P][4];
-};
-
-struct Pl {
-    int tok[6], bon[5], pres, nres, rev, res[3];
-};
-
-__device__ __forceinline__ Pl unpack_pl(const uint32_t w[4]) {
-    Pl p;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) p.tok[c] = (int)bget(w[0], c);
-    p.tok[4] = (int)bget(w[1], 0);
-    p.tok[5] = (int)bget(w[1], 1);
-    p.bon[0] = (int)bget(w[1], 2);
-    p.bon[1] = (int)bget(w[1], 3);
-    p.bon[2] = (int)bget(w[2], 0);
-    p.bon[3] = (int)bget(w[2], 1);
-    p.bon[4] = (int)bget(w[2], 2);
-    p.pres = (int)bget(w[2], 3);
-    p.nres = (int)(w[3] & 3u);
-    p.rev = (int)((w[3] >> 2) & 7u);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) p.res[i] = (int)bget(w[3], i + 1);
-    return p;
-}
-
-__device__ __forceinline__ void pack_pl(const Pl &p, uint32_t w[4]) {
-#ifdef SPL_BOUNDS_CHECK
-    for (int c = 0; c < 6; ++c) SPL_CHECK(p.tok[c] >= 0 && p.tok[c] <= 255, BC_BYTE);
-    for (int c = 0; c < 5; ++c) SPL_CHECK(p.bon[c] >= 0 && p.bon[c] <= 255, BC_BYTE);
-    SPL_CHECK(p.pres >= 0 && p.pres <= 255 && p.nres >= 0 && p.nres <= 3, BC_BYTE);
-#endif
-    w[0] = (uint32_t)p.tok[0] | ((uint32_t)p.tok[1] << 8) | ((uint32_t)p.tok[2] << 16) | ((uint32_t)p.tok[3] << 24);
-    w[1] = (uint32_t)p.tok[4] | ((uint32_t)p.tok[5] << 8) | ((uint32_t)p.bon[0] << 16) | ((uint32_t)p.bon[1] << 24);
-    w[2] = (uint32_t)p.bon[2] | ((uint32_t)p.bon[3] << 8) | ((uint32_t)p.bon[4] << 16) | ((uint32_t)p.pres << 24);
-    w[3] = ((uint32_t)p.nres & 3u) | (((uint32_t)p.rev & 7u) << 2) | (((uint32_t)p.res[0] & 0xFFu) << 8) |
-           (((uint32_t)p.res[1] & 0xFFu) << 16) | (((uint32_t)p.res[2] & 0xFFu) << 24);
-}
-
-template <int P>
-__device__ __forceinline__ void get_player(const Tab<P> &T, int p, uint32_t w[4]) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        // launder every player's word first: an asm inside the select would be executed
-        // conditionally, i.e. compiled into one branch per word
-        uint32_t o[P];
-#pragma unroll
-        for (int q = 0; q < P; ++q) o[q] = opaque(T.pw[q][k]);
-        uint32_t v = o[0];
-#pragma unroll
-        for (int q = 1; q < P; ++q) v = (p == q) ? o[q] : v;
-        w[k] = v;
-    }
-}
-
-template <int P>
-__device__ __forceinline__ void put_player(Tab<P> &T, int p, const uint32_t w[4]) {
-#pragma unroll
-    for (int q = 0; q < P; ++q)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) T.pw[q][k] = (p == q) ? w[k] : T.pw[q][k];
-}
-
-__device__ __forceinline__ void get_bank(const uint32_t *sw, int bank[6]) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) bank[c] = (int)bget(sw[SW_BANK0], c);
-    bank[4] = (int)bget(sw[SW_BANK1], 0);
-    bank[5] = (int)bget(sw[SW_BANK1], 1);
-}
-
-__device__ __forceinline__ void put_bank(uint32_t *sw, const int bank[6]) {
-#ifdef SPL_BOUNDS_CHECK
-    for (int c = 0; c < 6; ++c) SPL_CHECK(bank[c] >= 0 && bank[c] <= 255, BC_BYTE);
-#endif
-    sw[SW_BANK0] = (uint32_t)bank[0] | ((uint32_t)bank[1] << 8) | ((uint32_t)bank[2] << 16) | ((uint32_t)bank[3] << 24);
-    sw[SW_BANK1] = (sw[SW_BANK1] & 0xFFFF0000u) | (uint32_t)bank[4] | ((uint32_t)bank[5] << 8);
-}
-
-__device__ __forceinline__ int board_get(const uint32_t *sw, int k) {  // runtime k
-    const uint32_t b0 = opaque(sw[SW_BOARD]), b1 = opaque(sw[SW_BOARD + 1]), b2 = opaque(sw[SW_BOARD + 2]);
-    const uint32_t w = k < 4 ? b0 : (k < 8 ? b1 : b2);
-    return (int)bget(w, k & 3);
-}
-__device__ __forceinline__ void board_set(uint32_t *sw, int k, uint32_t v) {  // runtime k
-#pragma unroll
-    for (int t = 0; t < 3; ++t) sw[SW_BOARD + t] = (k >> 2) == t ? bset(sw[SW_BOARD + t], k & 3, v) : sw[SW_BOARD + t];
-}
-
-__device__ __forceinline__ uint4 card_rec(const Consts &L, int id) { return L.cards[id < 90 ? id : 0]; }
-
-__device__ __forceinline__ int card_cost(uint4 rec, int c) { return c < 4 ? (int)bget(rec.z, c) : (int)bget(rec.w, 0); }
-
-// Packed 16-bit arithmetic for per-colour comparisons: two colours per dword, saturating
-// subtraction in one v_pk_sub_u16 (clamp).  Byte fields are widened with one v_perm_b32.
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t sat_sub16(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(u16x2, a),
-                                                                      __builtin_bit_cast(u16x2, b)));
-}
-// bytes i and j of w as the low and high 16-bit halves
-__device__ __forceinline__ uint32_t widen2(uint32_t w, int i, int j) {
-    return __builtin_amdgcn_perm(0u, w, 0x0C000C00u | ((uint32_t)j << 16) | (uint32_t)i);
-}
-
-// what the player can put toward each colour: tokens + bonuses, packed (w|b, g|r, k) + gold
-struct Have {
-    uint32_t wb, gr, k;
-    int gold;
-};
-__device__ __forceinline__ Have have_of(const Pl &p) {
-    Have h;
-    h.wb = (uint32_t)(p.tok[0] + p.bon[0]) | ((uint32_t)(p.tok[1] + p.bon[1]) << 16);
-    h.gr = (uint32_t)(p.tok[2] + p.bon[2]) | ((uint32_t)(p.tok[3] + p.bon[3]) << 16);
-    h.k = (uint32_t)(p.tok[4] + p.bon[4]);
-    h.gold = p.tok[5];
-    return h;
-}
-
-// engine/state.py:61-71 can_afford: sum over colours of max(cost - bonus - tokens, 0) <= gold
-// (max(max(cost - bonus, 0) - tokens, 0) == max(cost - bonus - tokens, 0) for tokens >= 0)
-__device__ __forceinline__ bool afford(const Have &h, uint4 rec) {
-    const uint32_t s = sat_sub16(widen2(rec.z, 0, 1), h.wb) + sat_sub16(widen2(rec.z, 2, 3), h.gr);
-    const int need = (int)(s & 0xFFFFu) + (int)(s >> 16) + max((int)bget(rec.w, 0) - (int)h.k, 0);
-    return h.gold >= need;
-}
-
-// engine/rules.py:40-93 legal_moves -> 45-bit mask
-__device__ __forceinline__ uint64_t legal_mask(const uint32_t *sw, const Pl &p, const int bank[6], const Consts &L) {
-    uint32_t avail = 0;
-#pragma unroll
-    for (int c = 0; c < 5; ++c) avail |= (bank[c] >= 1 ? 1u : 0u) << c;
-    const int nav = __popc(avail);
-    uint64_t m = 0;
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {  // :45-58 reduced take-3 rule
-        const uint32_t cm = take3_mask(i);
-        const bool ok = nav >= 3 ? ((cm & avail) == cm) : (nav >= 1 && (avail & cm) == avail);
-        m |= (uint64_t)ok << i;
-    }
-#pragma unroll
-    for (int c = 0; c < 5; ++c) m |= (uint64_t)(bank[c] >= 4) << (10 + c);  // :61-63
-    const bool can_res = p.nres < 3;
-    const Have h = have_of(p);
-    // every card record is read unconditionally (missing cards read record 0) and combined with
-    // bitwise ops: `present && afford(card_rec(...))` compiled into 15 branches, each an LDS read
-    // followed by its own lgkmcnt(0) wait — 15 serial LDS round trips per legal mask
-    uint4 rec[15];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) rec[k] = card_rec(L, (int)bget(sw[SW_BOARD + k / 4], k % 4));
-#pragma unroll
-    for (int i = 0; i < 3; ++i) rec[12 + i] = card_rec(L, p.res[i]);
-#pragma unroll
-    for (int k = 0; k < 12; ++k) {  // :66-80
-        const uint32_t present = bget(sw[SW_BOARD + k / 4], k % 4) != 0xFFu ? 1u : 0u;
-        const uint32_t aff = afford(h, rec[k]) ? 1u : 0u;
-        m |= (uint64_t)(present & aff) << (15 + k);
-        m |= (uint64_t)(present & (can_res ? 1u : 0u)) << (27 + k);
-    }
-#pragma unroll
-    for (int t = 0; t < 3; ++t) m |= (uint64_t)(can_res && bget(sw[SW_DECK], t) > 0) << (39 + t);  // :83-86
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {  // :89-91
-        const uint32_t held = i < p.nres ? 1u : 0u;
-        const uint32_t aff = afford(h, rec[12 + i]) ? 1u : 0u;
-        m |= (uint64_t)(held & aff) << (42 + i);
-    }
-    return m;
-}
-
-// engine/rules.py:40-93 restricted to one action (the env only needs mask[a]) ...
-__device__ __forceinline__ bool action_legal(const uint32_t *sw, const Pl &p, const int bank[6], int a,
-                                             const Consts &L) {
-    if (a < 10) {
-        uint32_t avail = 0;
-#pragma unroll
-        for (int c = 0; c < 5; ++c) avail |= (bank[c] >= 1 ? 1u : 0u) << c;
-        const int nav = __popc(avail);
-        const uint32_t cm = take3_mask(a);
-        return nav >= 3 ? ((cm & avail) == cm) : (nav >= 1 && (avail & cm) == avail);
-    }
-    if (a < 15) {
-        const int c = a - 10;
-        const int b = c == 0 ? bank[0] : (c == 1 ? bank[1] : (c == 2 ? bank[2] : (c == 3 ? bank[3] : bank[4])));
-        return b >= 4;
-    }
-    if (a < 27) {
-        const int id = board_get(sw, a - 15);
-        return id != 0xFF && afford(have_of(p), card_rec(L, id));
-    }
-    if (a < 39) return p.nres < 3 && board_get(sw, a - 27) != 0xFF;
-    if (a < 42) return p.nres < 3 && bget(sw[SW_DECK], a - 39) > 0;
-    const int i = a - 42;
-    const int r0 = opaque(p.res[0]), r1 = opaque(p.res[1]), r2 = opaque(p.res[2]);
-    return i < p.nres && afford(have_of(p), card_rec(L, i == 0 ? r0 : (i == 1 ? r1 : r2)));
-}
-
-// ... and whether ANY move is legal: with a non-gold colour in the bank some take-3 always is
-// (rules.py:45-58), otherwise fall back to the full mask (rare).
-__device__ __forceinline__ bool any_legal(const uint32_t *sw, const Pl &p, const int bank[6], const Consts &L) {
-    const bool some_colour = bank[0] > 0 || bank[1] > 0 || bank[2] > 0 || bank[3] > 0 || bank[4] > 0;
-    return some_colour || legal_mask(sw, p, bank, L) != 0ull;
-}
-
-// engine/rules.py:101-122 _pay_for_card
-__device__ __forceinline__ void pay_for_card(Pl &p, int bank[6], uint4 rec) {
-    const int gold_avail = p.tok[5];
-    int gold_spent = 0;
-#pragma unroll
-    for (int c = 0; c < 5; ++c) {
-        const int disc = max(card_cost(rec, c) - p.bon[c], 0);
-        const int spend = min(p.tok[c], disc);
-        p.tok[c] -= spend;
-        bank[c] += spend;
-        const int rem = disc - spend;
-        gold_spent += rem > 0 ? min(rem, gold_avail - gold_spent) : 0;
-    }
-    p.tok[5] -= gold_spent;
-    bank[5] += gold_spent;
-    const int colour = (int)bget(rec.w, 1);
-#pragma unroll
-    for (int c = 0; c < 5; ++c) p.bon[c] += colour == c ? 1 : 0;
-    p.pres += (int)bget(rec.x, 2);
-}
-
-__device__ __forceinline__ uint8_t *slot_rec(const KArena &A, int t, int slot) {
-    SPL_CHECK(t >= 0 && t < A.n, BC_TABLE);
-    SPL_CHECK(slot >= 0 && slot < kSlotRecords, BC_SLOT);
-    return A.slots + ((size_t)t * kSlotRecords + slot) * kSlotBytes;
-}
-// slot-record ring status (spl_layout.h)
-__device__ __forceinline__ int active_of(uint32_t misc) { return (int)((misc >> ST_ACTIVE_SHIFT) & 3u); }
-__device__ __forceinline__ int pend_of(uint32_t misc) { return (int)((misc >> ST_PEND_SHIFT) & 3u); }
-__device__ __forceinline__ uint32_t ring_bits(int active, int pend) {
-    return ((uint32_t)active << ST_ACTIVE_SHIFT) | ((uint32_t)pend << ST_PEND_SHIFT);
-}
-__device__ __forceinline__ const uint8_t *live_rec(const KArena &A, int t, uint32_t misc) {
-    return slot_rec(A, t, active_of(misc));
-}
-
-// engine/rules.py:125-129 _refill_slot / deck.pop() of tier t.  `top` is the card at
-// deck_len-1 of that tier, gathered from the live record at the top of the step (one action
-// pops at most one card, from the tier the action names: pop_tier()).
-__device__ __forceinline__ uint32_t deck_pop(uint32_t *sw, uint32_t top, int t) {
-    const int len = (int)bget(sw[SW_DECK], t);
-    if (len <= 0) return 0xFFu;
-    sw[SW_DECK] = bset(sw[SW_DECK], t, (uint32_t)(len - 1));
-    return top;
-}
-
-// legal_moves of every fresh deal (engine/rules.py:40-93 on state.py:181-211's table): every
-// take-3 and take-2 (bank 4 of each colour), every visible and blind reserve, no purchase — as long as
-// every card costs something.  A context whose card table has a free card (kTagFreeCard) never
-// publishes the constant: its reset lanes evaluate legal_moves of the dealt state (fresh_deal_mask,
-// or the deferred evaluation of step_ws).
-constexpr uint64_t kFreshDealMask = ((1ull << 15) - 1ull) | (((1ull << 15) - 1ull) << 27);
-
-// tier an action pops from: buy visible (:216-225) and reserve visible (:226-240) refill the
-// slot's tier, reserve blind (:241-249) draws from its tier; -1 for every other action
-__device__ __forceinline__ int pop_tier(int a) {
-    return (a >= 15 && a < 27) ? (a - 15) >> 2 : ((a >= 27 && a < 39) ? (a - 27) >> 2 : ((a >= 39 && a < 42) ? a - 39 : -1));
-}
-
-// pick the r-th colour (ascending) among non-gold colours the player holds
-__device__ __forceinline__ void return_one(Pl &p, int bank[6], int r) {
-    int seen = 0;
-#pragma unroll
-    for (int c = 0; c < 5; ++c) {
-        const bool has = p.tok[c] > 0;
-        const bool hit = has && seen == r;
-        p.tok[c] -= hit ? 1 : 0;
-        bank[c] += hit ? 1 : 0;
-        seen += has ? 1 : 0;
-    }
-}
-
-__device__ __forceinline__ int non_gold_kinds(const Pl &p) {
-    int n = 0;
-#pragma unroll
-    for (int c = 0; c < 5; ++c) n += p.tok[c] > 0 ? 1 : 0;
-    return n;
-}
-
-// engine/rules.py:150-185 auto_return_tokens on the full CPython MT stream (rare: seeds
-// outside the precomputed table, or a table entry that ran out of draws).
-__device__ __forceinline__ void token_return_mt(Pl &p, int bank[6], int remaining, uint64_t seed, uint32_t *mtx) {
-    MTStream ms;
-    ms.init(seed);
-    bool done = false;
-    auto draw = [&](uint32_t y) {  // rng.choice(choices) on output y
-        const int nch = non_gold_kinds(p);
-        const int kb = bit_length((uint32_t)nch);
-        const int r = (int)(y >> (32 - kb));
-        if (r < nch) {  // accepted
-            return_one(p, bank, r);
-            remaining -= 1;
-        }
-    };
-    const int limit = min(g_stream_limit, MTStream::kMaxOut);
-    for (int j = 0;; ++j) {
-        done = done || remaining <= 0 || non_gold_kinds(p) == 0;
-        if (!__any(!done)) break;
-        if (j >= limit) break;  // lanes still returning continue below
-        const uint32_t y = ms.next(j);
-        if (!done) draw(y);
-    }
-    // Continuation past the streamed outputs (crafted states with hundreds of tokens to return):
-    // one lane at a time, its full MT19937 state in the LDS region mtx, from output kMaxOut on.
-    for (uint64_t slow = __ballot(!done); slow; slow &= slow - 1) {
-        if (lane_id() == __ffsll((unsigned long long)slow) - 1) {
-            LaneMT mt{mtx, 0};
-            mt.init(seed);
-            mt.start_at(limit);
-            while (remaining > 0 && non_gold_kinds(p) > 0) draw(mt.next());
-        }
-    }
-    if (remaining > 0 && p.tok[5] > 0) {
-        const int give = min(remaining, p.tok[5]);
-        p.tok[5] -= give;
-        bank[5] += give;
-    }
-}
-
-// token-return table index of (turn_count, to_play, sum(tokens), sum(bank)), -1 outside it
-__device__ __forceinline__ int lut_key(int turn_count, int to_play, int total, int bank_total) {
-    const bool in_lut = turn_count < kLutTc && to_play < kLutTp && total >= 11 && total <= 13 && bank_total < kLutSb;
-    return in_lut ? ((turn_count * kLutTp + to_play) * kLutSt + (total - 11)) * kLutSb + bank_total : -1;
-}
-
-// The table entry action `a` will consult, predicted from the pre-action state so its load
-// can start with the state loads: takes and reserves move tokens bank -> player exactly as
-// apply_action does; buys only lower the mover's total (-1: no prediction).
-__device__ __forceinline__ int predict_lut_key(const Pl &p, const int bank[6], int a, int turn_count, int to_play) {
-    int total = 0, bank_total = 0, delta = 0;
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-        total += p.tok[c];
-        bank_total += bank[c];
-    }
-    if (a < 10) {
-        const uint32_t cm = take3_mask(a);
-#pragma unroll
-        for (int c = 0; c < 5; ++c) delta += (((cm >> c) & 1u) && bank[c] >= 1) ? 1 : 0;
-    } else if (a < 15) {
-        delta = 2;
-    } else if (a >= 27 && a < 42) {
-        delta = bank[5] > 0 ? 1 : 0;
-    } else {
-        return -1;
-    }
-    return total + delta > 10 ? lut_key(turn_count, to_play, total + delta, bank_total - delta) : -1;
-}
-
-// engine/rules.py:150-185 auto_return_tokens on the table entry `e` (top 3 bits of the first
-// 40 outputs of the seeded stream, 10 per word).  One draw per iteration for every lane still
-// returning: rng.choice -> _randbelow(n) takes the top bit_length(n) bits of one output and
-// rejects r >= n; an accepted r returns one token of the r-th held non-gold colour.  The loop
-// exit is wave-uniform and the body predicated, so divergent rejection counts cost no nested
-// control flow.  Returns false if the lane needs more than the table's 40 outputs.
-__device__ __forceinline__ bool token_return_lut(Pl &p, int bank[6], int remaining, uint4 e) {
-    // On this path the mover holds 11..13 tokens, so every count fits a nibble: `tk` holds the
-    // five non-gold counts, `list` the held colours in ascending order (CPython's `choices`
-    // list, rebuilt after every draw in the reference) and `n` its length.  A draw reads the
-    // r-th entry of the list; a colour that runs out is cut out of it.  All 32-bit ops.
-    uint32_t tk = 0, list = 0;
-    int n = 0;
-#pragma unroll
-    for (int c = 0; c < 5; ++c) {
-        tk |= (uint32_t)p.tok[c] << (4 * c);
-        const bool has = p.tok[c] > 0;
-        list |= has ? (uint32_t)c << (4 * n) : 0u;
-        n += has ? 1 : 0;
-    }
-    bool active = remaining > 0 && n > 0;
-    // every lane draws at the same position, so the output word and bit offset are uniform
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const uint32_t w = q == 0 ? e.x : (q == 1 ? e.y : (q == 2 ? e.z : e.w));
-#pragma unroll 1
-        for (int j = 0; j < 10; ++j) {
-            if (!__any(active)) goto drawn;
-            // _randbelow(n): top bit_length(n) of the 3 stored bits; shift 3 - bit_length(n)
-            // for n = 1..5 is 2, 1, 1, 0, 0 (nibbles of 0x1120)
-            const uint32_t r = __builtin_amdgcn_ubfe(w, 3u * (uint32_t)j, 3u) >> ((0x1120u >> (4 * n)) & 15u);
-            const bool acc = active && (int)r < n;
-            const uint32_t c4 = 4u * __builtin_amdgcn_ubfe(list, 4u * r, 4u);  // nibble of the colour in tk
-            tk -= acc ? (1u << c4) : 0u;
-            const bool out = acc && ((tk >> c4) & 15u) == 0u;
-            const uint32_t low = (1u << (4u * r)) - 1u;  // cut entry r out of the list
-            list = out ? ((list & low) | ((list >> ((4u * r + 4u) & 31u)) << (4u * r))) : list;
-            n -= out ? 1 : 0;
-            remaining -= acc ? 1 : 0;
-            active = active && remaining > 0 && n > 0;
-        }
-    }
-drawn:
-    if (remaining > 0 && n > 0) return false;  // table outputs exhausted
-#pragma unroll
-    for (int c = 0; c < 5; ++c) {
-        const int now = (int)((tk >> (4 * c)) & 15u);
-        bank[c] += p.tok[c] - now;
-        p.tok[c] = now;
-    }
-    if (remaining > 0 && p.tok[5] > 0) {              // :179-184 then gold
-        const int give = min(remaining, p.tok[5]);
-        p.tok[5] -= give;
-        bank[5] += give;
-    }
-    return true;
-}
-
-// engine/rules.py:188-193 _enforce_token_limit -> :150-185 auto_return_tokens.  `pre_key` /
-// `pre_e` are the prefetched table entry (predict_lut_key); any other key is loaded here.
-__device__ __forceinline__ void enforce_token_limit(Pl &p, int bank[6], int turn_count, int to_play,
-                                                    const uint4 *lut, int pre_key, uint4 pre_e, uint32_t *mtx) {
-    int total = 0, bank_total = 0;
-#pragma unroll
-    for (int c = 0; c < 6; ++c) total += p.tok[c];
-    if (total <= 10) return;
-#pragma unroll
-    for (int c = 0; c < 6; ++c) bank_total += bank[c];
-    const int key = lut_key(turn_count, to_play, total, bank_total);
-    const bool in_lut = key >= 0;
-    bool need_mt = !in_lut;
-    if (in_lut) {
-        SPL_CHECK(key < kLutEntries, BC_LUT);
-        const uint4 e = key == pre_key ? pre_e : lut[key];
-        Pl p2 = p;
-        int bank2[6];
-#pragma unroll
-        for (int c = 0; c < 6; ++c) bank2[c] = bank[c];
-        if (token_return_lut(p2, bank2, total - 10, e)) {
-            p = p2;
-#pragma unroll
-            for (int c = 0; c < 6; ++c) bank[c] = bank2[c];
-        } else {
-            need_mt = true;
-        }
-    }
-    if (need_mt) {
-        const uint64_t seed = ((uint64_t)turn_count * 1315423911ull) ^ ((uint64_t)to_play * 2654435761ull) ^
-                              ((uint64_t)total * 97531ull) ^ ((uint64_t)bank_total * 31337ull);
-        token_return_mt(p, bank, total - 10, seed, mtx);
-    }
-}
-
-// engine/rules.py:132-147 _grant_noble_if_applicable (first visible noble in slot order)
-__device__ __forceinline__ void grant_noble(uint32_t *sw, Pl &p, int to_play, const Consts &L) {
-    const int nn = (int)bget(sw[SW_DECK], 3);
-    uint32_t owners = (sw[SW_NOB1] >> 8) & 0x7FFFu;
-    bool granted = false;
-    const uint32_t bon_wb = (uint32_t)p.bon[0] | ((uint32_t)p.bon[1] << 16);
-    const uint32_t bon_gr = (uint32_t)p.bon[2] | ((uint32_t)p.bon[3] << 16);
-#pragma unroll
-    for (int s = 0; s < 5; ++s) {
-        const int idx = s < 4 ? (int)bget(sw[SW_NOB0], s) : (int)bget(sw[SW_NOB1], 0);
-        const bool visible = s < nn && ((owners >> (3 * s)) & 7u) == 0 && idx < 10;
-        const uint2 rec = L.nobles[idx < 10 ? idx : 0];
-        // requirement minus bonus, saturated, is zero in every colour
-        const uint32_t req_wb = widen2(rec.x, 1, 2);
-        const uint32_t req_gr = __builtin_amdgcn_perm(rec.y, rec.x, 0x0C040C03u);  // x.byte3 | y.byte0
-        const bool meets = (sat_sub16(req_wb, bon_wb) | sat_sub16(req_gr, bon_gr)) == 0u &&
-                           (int)bget(rec.y, 1) <= p.bon[4];
-        const bool take = !granted && visible && meets;
-        owners |= take ? ((uint32_t)(to_play + 1) << (3 * s)) : 0u;
-        p.pres += take ? (int)bget(rec.y, 2) : 0;
-        granted = granted || take;
-    }
-    sw[SW_NOB1] = (sw[SW_NOB1] & 0xFFu) | (owners << 8);
-}
-
-// engine/rules.py:290-303 compute_winner: key (prestige, -cards, -reserved); tie of the top
-// two keys -> None
-template <int P>
-__device__ __forceinline__ int compute_winner(const Tab<P> &T) {
-    // track the top two keys as values (a runtime-indexed key[] array would go to scratch)
-    int best = -1;
-    uint32_t kbest = 0, ksecond = 0;
-#pragma unroll
-    for (int q = 0; q < P; ++q) {
-        const Pl p = unpack_pl(T.pw[q]);
-        const int nb = p.bon[0] + p.bon[1] + p.bon[2] + p.bon[3] + p.bon[4];
-        const uint32_t key = ((uint32_t)p.pres << 16) | ((uint32_t)(1023 - nb) << 4) | (uint32_t)(15 - p.nres);
-        if (q == 0) {
-            best = 0;
-            kbest = key;
-        } else if (key >= kbest) {
-            ksecond = kbest;
-            kbest = key;
-            best = q;
-        } else if (q == 1 || key >= ksecond) {
-            ksecond = key;
-        }
-    }
-    return kbest == ksecond ? -1 : best;
-}
-
-__device__ __forceinline__ int get_to_play(const uint32_t *sw) { return (int)bget(sw[SW_BANK1], 2); }
-__device__ __forceinline__ int get_turn(const uint32_t *sw) { return (int)bget(sw[SW_BANK1], 3); }
-__device__ __forceinline__ int get_moves(const uint32_t *sw) { return (int)(sw[SW_MISC] & 0xFFFFu); }
-__device__ __forceinline__ int get_winner(const uint32_t *sw) { return (int)(sw[SW_MISC] >> 24) - 1; }
-__device__ __forceinline__ bool is_terminal(const uint32_t *sw) {
-    return (sw[SW_MISC] & ST_GAME_OVER) && get_to_play(sw) == 0;
-}
-
-// engine/rules.py:196-287 apply_action on the current player (action known legal)
-template <int P, class Stamp>
-__device__ __forceinline__ void apply_action(Tab<P> &T, int a, uint32_t top, const Consts &L, const uint4 *lut,
-                                             int pre_key, uint4 pre_e, uint32_t *mtx, Stamp stamp) {
-    uint32_t *sw = T.sw;
-    const int tp = get_to_play(sw);
-    uint32_t w[4];
-    get_player(T, tp, w);
-    Pl p = unpack_pl(w);
-    int bank[6];
-    get_bank(sw, bank);
-    if (a < 10) {  // :201-210 take-3 (only colours still in the bank)
-        const uint32_t cm = take3_mask(a);
-#pragma unroll
-        for (int c = 0; c < 5; ++c) {
-            const bool take = ((cm >> c) & 1u) && bank[c] >= 1;
-            bank[c] -= take ? 1 : 0;
-            p.tok[c] += take ? 1 : 0;
-        }
-    } else if (a < 15) {  // :211-215 take-2
-#pragma unroll
-        for (int c = 0; c < 5; ++c) {
-            bank[c] -= (a - 10) == c ? 2 : 0;
-            p.tok[c] += (a - 10) == c ? 2 : 0;
-        }
-    } else if (a < 27) {  // :216-225 buy visible, refill
-        const int k = a - 15;
-        pay_for_card(p, bank, card_rec(L, board_get(sw, k)));
-        board_set(sw, k, deck_pop(sw, top, k >> 2));
-    } else if (a < 39) {  // :226-240 reserve visible, gold if any, refill
-        const int k = a - 27;
-        const int card = board_get(sw, k);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) p.res[i] = p.nres == i ? card : p.res[i];
-        p.rev |= 1 << p.nres;
-        p.nres += 1;
-        const bool gold = bank[5] > 0;
-        bank[5] -= gold ? 1 : 0;
-        p.tok[5] += gold ? 1 : 0;
-        board_set(sw, k, deck_pop(sw, top, k >> 2));
-    } else if (a < 42) {  // :241-249 reserve blind (hidden), gold if any
-        const int card = (int)deck_pop(sw, top, a - 39);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) p.res[i] = p.nres == i ? card : p.res[i];
-        p.rev &= ~(1 << p.nres);
-        p.nres += 1;
-        const bool gold = bank[5] > 0;
-        bank[5] -= gold ? 1 : 0;
-        p.tok[5] += gold ? 1 : 0;
-    } else {  // :250-255 buy reserved: list.pop(i) shifts later slots
-        const int i = a - 42;
-        const int r0 = opaque(p.res[0]), r1 = opaque(p.res[1]), r2 = opaque(p.res[2]);
-        const int card = i == 0 ? r0 : (i == 1 ? r1 : r2);
-        p.res[0] = i == 0 ? r1 : r0;
-        p.res[1] = i <= 1 ? r2 : r1;
-        p.res[2] = 0xFF;
-        p.rev = (p.rev & ((1 << i) - 1)) | ((p.rev >> (i + 1)) << i);
-        p.nres -= 1;
-        pay_for_card(p, bank, card_rec(L, card));
-    }
-    stamp(8);
-    if (!abl(ABL_NOBLE)) grant_noble(sw, p, tp, L);                         // :260
-    stamp(9);
-    if (!abl(ABL_TOKLIM)) enforce_token_limit(p, bank, get_turn(sw), tp, lut, pre_key, pre_e, mtx);  // :261
-    stamp(10);
-    uint32_t misc = sw[SW_MISC];
-    if (p.pres >= 15) misc |= ST_GAME_OVER;                                 // :264-265
-    pack_pl(p, w);
-    put_player(T, tp, w);
-    put_bank(sw, bank);
-    const int moves = (int)(misc & 0xFFFFu) + 1;                            // :268-272
-    const int ntp = (tp + 1) % P;
-    const int turn = moves / 2 + 1;
-    misc = (misc & 0xFFFF0000u) | (uint32_t)moves;
-    sw[SW_BANK1] = (sw[SW_BANK1] & 0x0000FFFFu) | ((uint32_t)ntp << 16) | ((uint32_t)min(turn, 255) << 24);
-    if (turn >= 100) {                                                      // :275-279
-        misc |= ST_GAME_OVER | ST_TURN_LIMIT;
-        misc &= 0x00FFFFFFu;  // winner None
-    } else if ((misc & ST_GAME_OVER) && ntp == 0) {                         // :282-285
-        sw[SW_MISC] = misc;
-        const int wnr = compute_winner(T);
-        misc = (misc & 0x00FFFFFFu) | ((uint32_t)(wnr + 1) << 24);
-    }
-    sw[SW_MISC] = misc;
-}
 
 // ------------------------------------------------------------------------------------------
 // observation (engine/encode.py:124-187) into the wave's LDS row block, as bytes

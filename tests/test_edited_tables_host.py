@@ -8,7 +8,7 @@ import pytest
 import edited_tables as et
 from oracle.oracle import Oracle
 
-FRESH = ((1 << 15) - 1) | (((1 << 15) - 1) << 27)  # kFreshDealMask (csrc/spl_engine.hip)
+FRESH = ((1 << 15) - 1) | (((1 << 15) - 1) << 27)  # kFreshDealMask (csrc/spl_engine_rules.h)
 
 
 @pytest.fixture(scope="module")

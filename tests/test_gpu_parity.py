@@ -132,7 +132,7 @@ def test_trajectories_c2_2000_plies(orc):
 
 @pytest.mark.parametrize("n", [984, 1000, 520, 4104])
 def test_xcd_map_ragged_grids(orc, n):
-    """The XCD-contiguous workgroup map (spl_engine.hip wg_block) on grids whose workgroup
+    """The XCD-contiguous workgroup map (spl_engine_base.h wg_block) on grids whose workgroup
     count is a multiple of 8 with a partial last block (984, 1000: 16 workgroups, the last one 24 / 40
     tables; 4104: 72 workgroups at 32 tables per workgroup) and on one that is not (520: 9 workgroups,
     identity map): every ply of k_step_ws bit-compared with the oracle, then a 48-step rollout store

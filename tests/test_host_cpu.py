@@ -414,11 +414,11 @@ def test_single_hip_runtime_after_load():
 
 
 def test_fresh_deal_mask_constant():
-    """step_ws's autoreset mask is the constant kFreshDealMask (spl_engine.hip): legal_moves of
+    """step_ws's autoreset mask is the constant kFreshDealMask (spl_engine_rules.h): legal_moves of
     every fresh deal, checked here on the oracle over many deals and player counts."""
     import re
     from oracle.oracle import Oracle
-    src = open(os.path.join(REPO, "splendor-gym_amd", "csrc", "spl_engine.hip")).read()
+    src = open(os.path.join(REPO, "splendor-gym_amd", "csrc", "spl_engine_rules.h")).read()
     assert re.search(r"kFreshDealMask = \(\(1ull << 15\) - 1ull\) \| \(\(\(1ull << 15\) - 1ull\) << 27\)", src)
     want = ((1 << 15) - 1) | (((1 << 15) - 1) << 27)
     o = Oracle()

@@ -1,5 +1,5 @@
 """Ablation timing of k_step_ws: build variants of the engine with one phase compiled out
-(-DSPL_ABL=<bits>, see spl_engine.hip) and time each in its own process (HIP events around
+(-DSPL_ABL=<bits>, see spl_engine_args.h) and time each in its own process (HIP events around
 each eager launch, 2p tables, device random policy, refill every 16).
 
     python tools/ablate.py [--build-only] [--run] [--rollout] [--tables 16384,65536] [--rounds R] [variant ...]

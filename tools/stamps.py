@@ -4,7 +4,7 @@
     python tools/stamps.py            # build lib_stamps.so (every source with the product's flags plus
                                       # -DSPL_STAMPS and STAMP_DEFS, tools/variants.py) and run on the GPU
     (STAMP_T: tables, default 65536; --build-only here, --run on the box)
-Lane 0 of every wave stamps its phase boundaries (see STAMP(i) in spl_engine.hip); we report, per
+Lane 0 of every wave stamps its phase boundaries (see STAMP(i) in spl_engine_stamps.h); we report, per
 wave role and phase, the median and max over waves of the time since the kernel's first stamp (10 ns ticks).
 Stamped builds fence the scheduler around each stamp: read the SHARES, not the absolute length.
 """
