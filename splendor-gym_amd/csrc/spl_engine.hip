@@ -7,16 +7,23 @@
 // move_count, patched separately) and leave the CU as coalesced 16-byte int32x4 stores; masks
 // leave as packed bytes built from per-lane 45-bit words in LDS.
 //
-// This file is the engine's one translation unit (a kernel is launched from the file that defines it).  Its bottom
-// layers are headers, included below in layer order, which is the order their definitions always had; a layer
-// includes only layers below it:
+// This file is the engine's one translation unit (a kernel is launched from the file that defines it).  Every layer
+// without a kernel is a header, included in layer order, which is the order their definitions always had; a layer
+// includes only layers below it (tests/test_engine_headers.py):
 //   spl_engine_args.h      kernel argument blocks, build switches (SPL_ABL, SPL_CHECK), lane_id
 //   spl_engine_stamps.h    the SPL_STAMPS diagnostics                                  (on args)
 //   spl_engine_base.h      stream limit, defaults, wg_block, LDS blocks, small helpers
 //   spl_engine_rules.h     the rules on a table in registers                           (on args, base)
-// The layers above them are still sections of this file, bottom up: the observation encoder, the deal, one env
-// step, k_rollout, the two-wave kernels' shared part, spl_step's kernels, the hand-offs, the split-wave rollouts,
-// the utility kernels; then the host side.
+//   spl_engine_obs.h       the observation encoder and the block stores                (on args, base, rules)
+//   spl_engine_deal.h      the deal, PCG / pool / state I/O, legal_of, policy_action   (on args, base, rules)
+//   spl_engine_step.h      one env step of one table, autoreset, refill slots          (on the four bottom layers, deal)
+//   spl_engine_cols.h      the column-parallel final rows                              (on args, base)
+//   spl_engine_ws.h        what the multi-wave kernels share, the bounded waits' parts (on args, base, rules, step)
+//   spl_engine_handoff.h   delegation, the dealer wave, the partner hand-off           (on all above but stamps, cols)
+// What stays here needs the translation unit, in the order it always had: k_build_lut (between the deal and the step
+// include), k_rollout, spl_step's kernels and kStepKernels (before the hand-off include: a kernel and a device
+// variable keep their order in the host object), the split-wave rollouts and kRolloutKernels, the utility kernels;
+// then the host side and the C ABI.
 //
 // Reference semantics restated here (paths relative to the reference root):
 //   engine/rules.py:40-93 legal_moves, :101-122 _pay_for_card, :125-129 _refill_slot,
@@ -45,647 +52,10 @@
 #include "spl_engine_stamps.h"
 #include "spl_engine_base.h"
 #include "spl_engine_rules.h"
+#include "spl_engine_obs.h"
+#include "spl_engine_deal.h"
 
 namespace spl {
-
-// ------------------------------------------------------------------------------------------
-// observation (engine/encode.py:124-187) into the wave's LDS row block, as bytes
-// ------------------------------------------------------------------------------------------
-// The wave's rows are packed back to back (row r at byte 297r), so most fields of a lane's row
-// sit at unaligned LDS addresses: written field by field they compile to unaligned ds_write_b96
-// / b32 accesses that stall the LDS pipe (SQ_LDS_UNALIGNED_STALL) and to ~35 byte writes per row.
-// Instead each lane assembles its 297 bytes as 75 dwords in registers (R[j] = bytes 4j..4j+3;
-// every offset is a compile-time constant, so R stays in VGPRs) and writes the ALIGNED dwords
-// that start inside its row, shifted into place with v_alignbyte_b32; the dword that straddles
-// rows L and L+1 is completed with row L+1's first bytes (its bank counts) taken from lane L+1.
-
-// n bytes of v at byte offset o of the row (o, n compile-time after unrolling)
-__device__ __forceinline__ void rput(uint32_t (&R)[76], int o, int n, uint32_t v) {
-    if (n < 4) v &= (1u << (8 * n)) - 1u;
-    const int j = o >> 2, sh = (o & 3) * 8;
-    R[j] |= v << sh;
-    if (sh != 0 && (o & 3) + n > 4) R[j + 1] |= v >> (32 - sh);
-}
-
-__device__ __forceinline__ void rput_card13(uint32_t (&R)[76], int o, uint4 rec, bool present) {
-    rput(R, o, 4, present ? rec.x : 0u);
-    rput(R, o + 4, 4, present ? rec.y : 0u);
-    rput(R, o + 8, 4, present ? rec.z : 0u);
-    rput(R, o + 12, 1, present ? rec.w : 0u);
-}
-
-// The 297 observation bytes of table T as dwords R[0..74] (R[75] = 0).
-template <int P>
-__device__ __forceinline__ void build_row(const Tab<P> &T, const Consts &L, uint32_t (&R)[76]) {
-    const uint32_t *sw = T.sw;
-    const int tp = get_to_play(sw);
-#pragma unroll
-    for (int j = 0; j < 76; ++j) R[j] = 0u;
-    rput(R, 0, 4, sw[SW_BANK0]);                // bank :128
-    rput(R, 4, 2, sw[SW_BANK1]);
-    uint32_t me[4], op[4];
-    get_player(T, tp, me);                      // current :131-135
-    get_player(T, (tp + 1) % P, op);            // opponent = next player :138-142
-    rput(R, 6, 4, me[0]);
-    rput(R, 10, 4, me[1]);
-    rput(R, 14, 4, me[2]);
-    rput(R, 18, 1, me[3] & 3u);
-    rput(R, 19, 4, op[0]);
-    rput(R, 23, 4, op[1]);
-    rput(R, 27, 4, op[2]);
-    rput(R, 31, 1, op[3] & 3u);
-#pragma unroll
-    for (int k = 0; k < 12; ++k) {              // board :144-147
-        const int id = (int)bget(sw[SW_BOARD + k / 4], k % 4);
-        rput_card13(R, 32 + 13 * k, card_rec(L, id), id != 0xFF);
-    }
-    const int mn = (int)(me[3] & 3u), on = (int)(op[3] & 3u), orev = (int)((op[3] >> 2) & 7u);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {               // own reserved, always revealed :151-155
-        const bool pr = i < mn;
-        rput_card13(R, 188 + 14 * i, card_rec(L, (int)bget(me[3], i + 1)), pr);
-        rput(R, 188 + 14 * i + 13, 1, pr ? 1u : 0u);
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {               // opponent reserved, hidden -> zeros :158-168
-        const bool pr = i < on && ((orev >> i) & 1);
-        rput_card13(R, 230 + 14 * i, card_rec(L, (int)bget(op[3], i + 1)), pr);
-        rput(R, 230 + 14 * i + 13, 1, pr ? 1u : 0u);
-    }
-    const int nn = (int)bget(sw[SW_DECK], 3);
-    const uint32_t owners = (sw[SW_NOB1] >> 8) & 0x7FFFu;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {               // nobles[:3] :171-178
-        const int idx = (int)bget(sw[SW_NOB0], i);
-        const bool pr = i < nn && ((owners >> (3 * i)) & 7u) == 0 && idx < 10;
-        const uint2 rec = L.nobles[idx < 10 ? idx : 0];
-        rput(R, 272 + 6 * i, 4, pr ? rec.x : 0u);
-        rput(R, 276 + 6 * i, 2, pr ? rec.y : 0u);
-    }
-    rput(R, 290, 3, sw[SW_DECK]);               // deck sizes :180-181
-    rput(R, 293, 1, (uint32_t)get_turn(sw));    // misc :183-186
-    rput(R, 294, 1, (uint32_t)tp);
-    rput(R, 295, 1, (uint32_t)get_moves(sw));   // > 255 patched after the block store
-    rput(R, 296, 1, is_terminal(sw) ? 1u : 0u);
-}
-
-// Row of table T into rows_base[297*lane ...].  Every lane of the wave must call it (the row
-// boundaries are shared with the neighbouring lanes); rows of lanes whose table is not needed
-// are written too and simply not stored.
-template <int P>
-__device__ __forceinline__ void encode_row(const Tab<P> &T, uint8_t *rows_base, const Consts &L) {
-    uint32_t R[76];
-    build_row(T, L, R);
-    // bytes 297..299: the next lane's row bytes 0..2 (its bank counts)
-    R[74] |= (uint32_t)__shfl_down((int)R[0], 1) << 8;
-    const int lane = lane_id();
-    const uint32_t o0 = (4u - ((uint32_t)lane & 3u)) & 3u;  // row 297*lane starts at lane mod 4
-    uint32_t *dst = reinterpret_cast<uint32_t *>(rows_base + kObsDim * lane + o0);
-#pragma unroll
-    for (int j = 0; j < 74; ++j) dst[j] = __builtin_amdgcn_alignbyte(R[j + 1], R[j], o0);
-    if (o0 == 0u) dst[74] = R[74];
-}
-
-// Half of encode_row: staged dwords [0, kRowHalf) (Half 0) or [kRowHalf, 75) (Half 1) of every
-// lane's row, so two waves of a workgroup encode one block in parallel.  build_row is inlined
-// with constant indices, so each half computes only the row bytes its dwords take.
-constexpr int kRowHalf = 37;
-template <int Half, int P>
-__device__ __forceinline__ void encode_row_half(const Tab<P> &T, uint8_t *rows_base, const Consts &L) {
-    uint32_t R[76];
-    build_row(T, L, R);
-    if (Half == 1) R[74] |= (uint32_t)__shfl_down((int)R[0], 1) << 8;
-    const int lane = lane_id();
-    const uint32_t o0 = (4u - ((uint32_t)lane & 3u)) & 3u;
-    uint32_t *dst = reinterpret_cast<uint32_t *>(rows_base + kObsDim * lane + o0);
-    constexpr int j0 = Half == 0 ? 0 : kRowHalf, j1 = Half == 0 ? kRowHalf : 74;
-#pragma unroll
-    for (int j = j0; j < j1; ++j) dst[j] = __builtin_amdgcn_alignbyte(R[j + 1], R[j], o0);
-    if (Half == 1 && o0 == 0u) dst[74] = R[74];
-}
-
-// The compact observation row (spl_step_args_t.obs_u8) of table T at rows_base[300*lane ...]:
-// the row's 297 bytes, move_count >> 8, two zero bytes — 75 aligned dwords per row (no
-// neighbouring-lane bytes).  Part 0: dwords [0, kRowHalf), 1: [kRowHalf, 75), 2: all.
-template <int Part, int P>
-__device__ __forceinline__ void encode_row_u8(const Tab<P> &T, uint8_t *rows_base, const Consts &L) {
-    uint32_t R[76];
-    build_row(T, L, R);
-    R[74] = (R[74] & 0xFFu) | ((uint32_t)(get_moves(T.sw) >> 8) << 8);
-    uint32_t *dst = reinterpret_cast<uint32_t *>(rows_base + kObsU8 * lane_id());
-    constexpr int j0 = Part == 1 ? kRowHalf : 0, j1 = Part == 0 ? kRowHalf : 75;
-#pragma unroll
-    for (int j = j0; j < j1; ++j) dst[j] = R[j];
-}
-
-// Observation of table T written by its own lane straight to dst[0..296] (int32; 297 dword
-// stores): the rare path for terminal rows that do not fit the pipelined kernel's hand-off.
-template <int P>
-__device__ __forceinline__ void store_row_direct(const Tab<P> &T, const Consts &L, int32_t *dst) {
-    uint32_t R[76];
-    build_row(T, L, R);
-#pragma unroll
-    for (int e = 0; e < kObsDim; ++e) dst[e] = e == 295 ? get_moves(T.sw) : (int32_t)bget(R[e >> 2], e & 3);
-}
-
-// Block store of this wave's staged rows: obs[t0 .. t0+rows) as int32, 16 B per lane-store.
-// LDS reads are issued in groups of 5 before their stores: one read-wait per store halves the
-// store rate (tools/microbench_store.hip: 2.7 -> 5.2 TB/s).
-// One 16-byte store per lane per instruction, typed as a native 4 x i32 vector indexed in vector
-// units: with `int4` and 32-bit element indexing the compiler versions the loop and, in the
-// unrolled copy, splits every store into four strided dword stores (half the store bandwidth).
-typedef int v4i __attribute__((ext_vector_type(4)));
-
-// The two output streams of a rollout.  NT: the per-step rollout store's row and mask blocks (written once
-// and not read back by this launch) leave non-temporal, so the 5 GB stream does not push the token table,
-// deck records and state out of L2 / the Infinity Cache — the rules wave's gathers stay fast (rollout store
-// 1225 -> 1109 us per 64 steps at 65 536 tables; plain 13-22 % slower in the kernel, profiles/r06/roll_nt_ab_r06m.txt).
-// In-place outputs keep plain stores: their block stays Infinity-Cache resident for the consumer (NT: 794 ->
-// 1020 us).  So do the store's terminal rows and small outputs (through the NT stream: headline 1 972-1 984 vs
-// 1 936-1 955 us, C4 1 177-1 178 vs 1 065-1 067; profiles/r06/small_outputs_nt_ab_r06ai.txt).
-// The NT stream is a buffer store with a cache-policy immediate (gfx950: sc0 = 1, nt = 2, sc1 = 16) on a
-// resource over the block: 19 = `sc0 nt sc1` (system scope, non-temporal), headline 1 941-1 952 against
-// 1 975-2 002 us per launch with `nt` alone, four alternations on one box, 1.4 % on another; without nt
-// 12 % slower (profiles/r06/store_policy_ab_r06u_v.txt)
-constexpr int kRollCpol = 19;
-constexpr int kPlainCpol = -2;
-typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
-// 16-byte output stores into one wave-uniform block under cache policy CP: kPlainCpol plain stores, >= 0 a
-// buffer store with that cache-policy immediate
-template <int CP>
-struct V4Sink {
-    v4i *out;
-    __amdgpu_buffer_rsrc_t rs;
-    __device__ __forceinline__ explicit V4Sink(void *p) : out(reinterpret_cast<v4i *>(p)) {
-        if constexpr (CP >= 0) rs = __builtin_amdgcn_make_buffer_rsrc(p, (short)0, 0x7FFFFFF0, 0x00020000);
-    }
-    __device__ __forceinline__ void put(int i, v4i v) const {
-        if constexpr (CP >= 0) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, v), rs, i * 16, 0, CP);
-        else out[i] = v;
-    }
-};
-// the policy of an output stream: the NT stream or plain stores
-constexpr int stream_cpol(bool nt) { return nt ? kRollCpol : kPlainCpol; }
-
-__device__ __forceinline__ v4i expand4(uint32_t w) {
-    v4i v = {(int)(w & 0xFFu), (int)((w >> 8) & 0xFFu), (int)((w >> 16) & 0xFFu), (int)(w >> 24)};
-    return v;
-}
-
-// Part [d0, d1) (LDS words, multiples of 64*5 except the end) of a FULL wave's observation block.
-template <bool NT = false>
-__device__ __forceinline__ void store_obs_range(const uint8_t *rows_lds, int32_t *dst, int d0, int d1) {
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(rows_lds);
-    const V4Sink<stream_cpol(NT)> out(dst);
-    constexpr int U = 5;
-    int d = d0 + lane_id();
-#pragma unroll 1
-    for (; d + 64 * (U - 1) < d1; d += 64 * U) {
-        uint32_t w[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) w[u] = src[d + 64 * u];
-#pragma unroll
-        for (int u = 0; u < U; ++u) out.put(d + 64 * u, expand4(w[u]));
-    }
-    uint32_t w[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) w[u] = (d + 64 * u < d1) ? src[d + 64 * u] : 0u;
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-        if (d + 64 * u < d1) out.put(d + 64 * u, expand4(w[u]));
-}
-constexpr int kObsBlockWords = 64 * kObsDim / 4;  // 4752 LDS words = 4752 16-byte stores per wave
-constexpr int kObsSplit = 64 * 5 * 7;             // 2240: 35 stores per lane in the first part
-
-// Block store of this wave's observation rows: LDS bytes [rows][297] -> int32 [rows][297] at
-// dst (16-byte aligned: 64-row blocks are 76032 B).  Dword d of the block is LDS word d.
-// R = the workgroup's table count (64, or 32 in the half-populated two-wave rollout).
-template <int R = 64, bool NT = false, int CP = stream_cpol(NT)>
-__device__ __forceinline__ void store_obs_block(const uint8_t *rows_lds, int rows, int32_t *dst) {
-    const int nbytes = rows * kObsDim;
-    const int full = nbytes >> 2;
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(rows_lds);
-    const V4Sink<CP> out(dst);
-    constexpr int U = 5;
-    int d = lane_id();
-    if (rows == R) {  // every wave but a ragged last one: compile-time trip count
-        constexpr int kFull = R * kObsDim / 4;  // 64 rows: 4752 = 14 x 320 + 272
-#pragma unroll 1
-        for (int it = 0; it < kFull / (64 * U); ++it, d += 64 * U) {
-            uint32_t w[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) w[u] = src[d + 64 * u];
-#pragma unroll
-            for (int u = 0; u < U; ++u) out.put(d + 64 * u, expand4(w[u]));
-        }
-        uint32_t w[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) w[u] = (d + 64 * u < kFull) ? src[d + 64 * u] : 0u;
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-            if (d + 64 * u < kFull) out.put(d + 64 * u, expand4(w[u]));
-        return;
-    }
-    for (; d < full; d += 64) out.put(d, expand4(src[d]));
-    for (int b = (full << 2) + lane_id(); b < nbytes; b += 64) dst[b] = (int32_t)rows_lds[b];
-}
-
-// store_obs_block (64 rows) with `mid()` issued between its first and second half: work that fills the
-// wave's store-issue stalls instead of following the whole block (k_step_wso's legal mask).  Plain stores.
-template <class Mid>
-__device__ __forceinline__ void store_obs_block_mid(const uint8_t *rows_lds, int rows, int32_t *dst, Mid mid) {
-    if (rows != 64) {
-        mid();
-        store_obs_block<64, false>(rows_lds, rows, dst);
-        return;
-    }
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(rows_lds);
-    const V4Sink<kPlainCpol> out(dst);
-    constexpr int U = 5, kFull = 64 * kObsDim / 4, kIters = kFull / (64 * U);  // 4752 = 14 x 320 + 272
-    int d = lane_id();
-#pragma unroll 1
-    for (int it = 0; it < kIters / 2; ++it, d += 64 * U) {
-        uint32_t w[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) w[u] = src[d + 64 * u];
-#pragma unroll
-        for (int u = 0; u < U; ++u) out.put(d + 64 * u, expand4(w[u]));
-    }
-    __asm__ volatile("" ::: "memory");
-    mid();
-    __asm__ volatile("" ::: "memory");
-#pragma unroll 1
-    for (int it = kIters / 2; it < kIters; ++it, d += 64 * U) {
-        uint32_t w[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) w[u] = src[d + 64 * u];
-#pragma unroll
-        for (int u = 0; u < U; ++u) out.put(d + 64 * u, expand4(w[u]));
-    }
-    uint32_t w[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) w[u] = (d + 64 * u < kFull) ? src[d + 64 * u] : 0u;
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-        if (d + 64 * u < kFull) out.put(d + 64 * u, expand4(w[u]));
-}
-
-// Block store of `rows` compact rows (300 bytes each) staged in LDS to dst (16-byte aligned).
-__device__ __forceinline__ void store_obs_u8_block(const uint8_t *rows_lds, int rows, uint8_t *dst) {
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(rows_lds);
-    const int words = rows * (kObsU8 / 4), chunks = words >> 2;
-    v4i *out = reinterpret_cast<v4i *>(dst);
-    for (int c = lane_id(); c < chunks; c += 64) {
-        const v4i v = {(int)src[4 * c], (int)src[4 * c + 1], (int)src[4 * c + 2], (int)src[4 * c + 3]};
-        out[c] = v;
-    }
-    for (int w = 4 * chunks + lane_id(); w < words; w += 64) reinterpret_cast<uint32_t *>(dst)[w] = src[w];
-}
-
-// The compact rows (spl_step_args_t.obs_u8 layout: 297 bytes, move_count >> 8, two zero bytes) of
-// the wave's staged 297-byte rows, stored beside their int32 block when a step writes both: 75 dwords
-// per row, consecutive lanes on consecutive dwords (256-byte stores); dword j < 74 of row r is the
-// staged bytes 297 r + 4 j .. + 3 (one v_alignbyte of the two staged dwords around them), dword 74
-// is byte 296, move_count >> 8 (`mhi` of lane r, whose table is row r), 0, 0.  Every lane runs
-// every iteration (the row's high byte comes by shuffle), the stores are predicated.  With a 16-byte
-// aligned dst each lane builds four consecutive dwords (one 16-byte store; a chunk crosses at most one
-// row end, whose dword 74 belongs to the chunk's first row), 19 iterations for 64 rows instead of 75.
-__device__ __forceinline__ void store_u8_from_rows(const uint8_t *rows_lds, int rows, uint8_t *dst, uint32_t mhi) {
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(rows_lds);
-    uint32_t *out = reinterpret_cast<uint32_t *>(dst);
-    constexpr int kWords = kObsU8 / 4;  // 75
-    const int total = rows * kWords;
-    int q_first = 0;
-    if (((uintptr_t)dst & 15u) == 0) {
-        const int chunks = total >> 2;
-        v4i *out4 = reinterpret_cast<v4i *>(dst);
-        for (int it = 0; it < (chunks + 63) / 64; ++it) {
-            const int c = lane_id() + 64 * it, cc = c < chunks ? c : chunks - 1;
-            const int q0 = 4 * cc, r0 = q0 / kWords, j0 = q0 - kWords * r0;
-            const uint32_t h = (uint32_t)__shfl((int)mhi, r0);
-            v4i v;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const bool next = j0 + i >= kWords;  // past row r0's end: row r0 + 1 from its byte 0
-                const int j = next ? j0 + i - kWords : j0 + i;
-                const int b = kObsDim * (next ? r0 + 1 : r0) + 4 * j;
-                uint32_t w = __builtin_amdgcn_alignbyte(src[(b >> 2) + 1], src[b >> 2], (uint32_t)(b & 3));
-                if (j0 + i == kWords - 1) w = (w & 0xFFu) | (h << 8);
-                v[i] = (int)w;
-            }
-            if (c < chunks) out4[c] = v;
-        }
-        q_first = chunks << 2;
-    }
-    for (int it = 0; it < (total - q_first + 63) / 64; ++it) {
-        const int q = q_first + lane_id() + 64 * it, qq = q < total ? q : total - 1;
-        const int r = qq / kWords, j = qq - kWords * r;
-        const int b = kObsDim * r + 4 * j;  // staged byte; b / 4 + 1 <= 4 677 < 64 * 300 / 4
-        uint32_t v = __builtin_amdgcn_alignbyte(src[(b >> 2) + 1], src[b >> 2], (uint32_t)(b & 3));
-        const uint32_t h = (uint32_t)__shfl((int)mhi, r);
-        if (j == kWords - 1) v = (v & 0xFFu) | (h << 8);
-        if (q < total) out[q] = v;
-    }
-}
-
-// Block store of this wave's masks: mask[t0 .. t0+rows) as int8 [rows][45].  The 64 x 45 mask
-// bits are first laid out as ONE bit stream in LDS (row r at bits 45r..45r+44; each stream
-// dword is cut from at most two rows), so every output dword is one nibble of the stream,
-// spread to 4 bytes by a multiply: bit i of n moves to bit 8i in n * 0x204081.
-template <bool NT = false, int CP = stream_cpol(NT)>
-__device__ __forceinline__ void store_mask_block(const uint64_t *mask, uint32_t *mbits, int rows, int8_t *dst) {
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int w = lane_id() + 64 * k;  // stream dword w: bits 32w .. 32w+31
-        if (w < kMaskStreamWords) {
-            const int r0 = (32 * w) / 45, c0 = 32 * w - 45 * r0;  // first bit: row r0, column c0
-            const uint64_t m0 = mask[r0], m1 = r0 + 1 < 64 ? mask[r0 + 1] : 0ull;
-            // columns c0..44 of row r0, then row r0+1 from column 0
-            const uint64_t lo = m0 >> c0, hi = (c0 > 13) ? (m1 << (45 - c0)) : 0ull;
-            mbits[w] = (uint32_t)(lo | hi);
-        }
-    }
-    wave_lds_sync();
-    if ((rows == 64 || rows == 32) && ((uintptr_t)dst & 15u) == 0) {  // 180 (90) x 16 B
-        const V4Sink<CP> out4(dst);
-        const int nc = rows * 45 / 16;
-        for (int c = lane_id(); c < nc; c += 64) {
-            const uint32_t half = (mbits[c >> 1] >> (16 * (c & 1))) & 0xFFFFu;  // stream bits 16c..16c+15
-            v4i v;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) v[q] = (int)((((half >> (4 * q)) & 0xFu) * 0x00204081u) & 0x01010101u);
-            out4.put(c, v);
-        }
-        return;
-    }
-    const int nbytes = rows * 45;
-    const int full = nbytes >> 2;
-    uint32_t *out = reinterpret_cast<uint32_t *>(dst);
-    for (int d = lane_id(); d < full; d += 64) {
-        const uint32_t nib = (mbits[d >> 3] >> (4 * (d & 7))) & 0xFu;
-        out[d] = (nib * 0x00204081u) & 0x01010101u;
-    }
-    for (int b = (full << 2) + lane_id(); b < nbytes; b += 64)
-        dst[b] = (int8_t)((mbits[b >> 5] >> (b & 31)) & 1u);
-}
-
-// ------------------------------------------------------------------------------------------
-// deal: engine/state.py:181-211 initial_state's shuffles, from one engine seed
-// ------------------------------------------------------------------------------------------
-// Fisher–Yates (Lib/random.py:389-394) over tier 1, 2, 3 decks then the nobles, driven by ONE
-// uniform loop over MT outputs: every lane advances its own stream by one output per
-// iteration and its own shuffle state machine accepts or rejects it (_randbelow), so the cost
-// is the wave's maximum output count, not the sum of per-draw maxima.
-struct Deal {
-    uint32_t board[3], nob0, nob1;  // SW_BOARD.., SW_NOB0, SW_NOB1 of the dealt table
-};
-__device__ __forceinline__ Deal empty_deal() { return Deal{{0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, 0xFFFFFFFFu, 0xFFu}; }
-
-__device__ __forceinline__ uint32_t deal_into(uint32_t seed, int P, uint8_t *rec, uint8_t *scr, Deal &out,
-                                              uint32_t *mtx) {
-    for (int i = 0; i < 100; ++i) scr[i] = (uint8_t)(i < 90 ? i : i - 90);
-    MTStream ms;
-    ms.init(seed);
-    int d = 0, base = 0, i = 39;
-    uint32_t flags = 0;
-    // _randbelow(i + 1) on output y; a rejected draw (or a finished lane, or `on` false) swaps x[i]
-    // with itself.  The caller's LDS reads of the two bytes overlap the next output's computation.
-    auto shuffle_step = [&](uint32_t y, bool on, auto &&between) {
-        const int n = i + 1;
-        const int r = (int)(y >> (32 - bit_length((uint32_t)n)));
-        const bool acc = on && d < 4 && r < n;
-        const int ai = base + i, ar = base + (acc ? r : i);
-        SPL_CHECK(ai >= 0 && ai < 100 && ar >= 0 && ar < 100, BC_SCRATCH);
-        const uint8_t xi = scr[ai], xr = scr[ar];
-        between();
-        scr[ai] = xr;
-        scr[ar] = xi;
-        const int i2 = acc ? i - 1 : i;
-        const bool adv = acc && i2 == 0;  // deck finished: tier 2, tier 3, then the nobles
-        d += adv ? 1 : 0;
-        base = adv ? (d == 1 ? 40 : (d == 2 ? 70 : 90)) : base;
-        i = adv ? (d == 1 ? 29 : (d == 2 ? 19 : 9)) : i2;
-    };
-    const int limit = min(g_stream_limit, MTStream::kMaxOut);
-    uint32_t y = ms.next(0);
-    for (int j = 0;; ++j) {
-        if (!__any(d < 4)) break;
-        if (j >= limit) break;  // lanes still shuffling continue below
-        shuffle_step(y, true, [&] {
-            if (j + 1 < limit) y = ms.next(j + 1);
-        });
-    }
-    // Continuation past the streamed outputs (never met in natural play): one lane at
-    // a time, its full MT19937 state in the LDS region mtx, from output kMaxOut on.
-    for (uint64_t slow = __ballot(d < 4); slow; slow &= slow - 1) {
-        if (lane_id() == __ffsll((unsigned long long)slow) - 1) {
-            LaneMT mt{mtx, 0};
-            mt.init(seed);
-            mt.start_at(limit);
-            while (d < 4) shuffle_step(mt.next(), true, [] {});
-        }
-    }
-    // deck bytes (list order; the 4 dealt cards per tier sit past deck_len)
-    const uint32_t *s1 = reinterpret_cast<const uint32_t *>(scr);  // 4-byte aligned scratch
-    uint32_t *r1 = reinterpret_cast<uint32_t *>(rec);
-#pragma unroll
-    for (int q = 0; q < 24; ++q) r1[q] = s1[q];
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {  // board[tier][i] = deck.pop()
-        const int b = tier_base(t), n = tier_size(t);
-        out.board[t] = (uint32_t)scr[b + n - 1] | ((uint32_t)scr[b + n - 2] << 8) | ((uint32_t)scr[b + n - 3] << 16) |
-                       ((uint32_t)scr[b + n - 4] << 24);
-    }
-    const int nn = P + 1 < 10 ? P + 1 : 10;  // state.py:194 (<= 5 for P <= 4)
-    out.nob0 = 0;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) out.nob0 |= (s < nn ? (uint32_t)scr[90 + s] : 0xFFu) << (8 * s);
-    out.nob1 = nn > 4 ? (uint32_t)scr[94] : 0xFFu;
-    uint32_t *rw = reinterpret_cast<uint32_t *>(rec);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) rw[kRecTail / 4 + k] = out.board[k];
-    rw[kRecTail / 4 + 3] = out.nob0;
-    rw[kRecTail / 4 + 4] = out.nob1;
-    rw[kRecSeed / 4] = seed;
-    return flags;
-}
-
-// the board / noble words of a dealt record (its bytes 96..115)
-__device__ __forceinline__ Deal rec_deal(const uint8_t *rec) {
-    const uint32_t *rw = reinterpret_cast<const uint32_t *>(rec);
-    Deal d;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) d.board[k] = rw[kRecTail / 4 + k];
-    d.nob0 = rw[kRecTail / 4 + 3];
-    d.nob1 = rw[kRecTail / 4 + 4];
-    return d;
-}
-
-template <int P>
-__device__ __forceinline__ void fresh_state(Tab<P> &T, uint32_t status, const Deal &d) {
-    constexpr uint32_t nn = P + 1 < 10 ? P + 1 : 10;
-    T.sw[SW_BANK0] = 0x04040404u;                       // DEFAULT_BANK, state.py:26-33
-    T.sw[SW_BANK1] = 4u | (5u << 8) | (0u << 16) | (1u << 24);  // to_play 0, turn_count 1
-    T.sw[SW_MISC] = status;                              // move_count 0, winner None
-    T.sw[SW_BOARD] = d.board[0];
-    T.sw[SW_BOARD + 1] = d.board[1];
-    T.sw[SW_BOARD + 2] = d.board[2];
-    T.sw[SW_DECK] = 36u | (26u << 8) | (16u << 16) | (nn << 24);  // 40, 30, 20 minus the 4 dealt
-    T.sw[SW_NOB0] = d.nob0;
-    T.sw[SW_NOB1] = d.nob1;
-#pragma unroll
-    for (int q = 0; q < P; ++q) {
-        T.pw[q][0] = T.pw[q][1] = T.pw[q][2] = 0u;
-        T.pw[q][3] = 0xFFFFFF00u;
-    }
-}
-
-__device__ __forceinline__ Pcg64 load_pcg(const KArena &A, int t) {
-    const uint64_t *p = reinterpret_cast<const uint64_t *>(A.pcg + (size_t)t * kPcgBytes);
-    const uint32_t *q = reinterpret_cast<const uint32_t *>(p + 4);
-    Pcg64 g;
-    g.s_hi = p[0];
-    g.s_lo = p[1];
-    g.inc_hi = p[2];
-    g.inc_lo = p[3];
-    g.has32 = q[0];
-    g.u32 = q[1];
-    return g;
-}
-__device__ __forceinline__ void store_pcg(const KArena &A, int t, const Pcg64 &g) {
-    uint64_t *p = reinterpret_cast<uint64_t *>(A.pcg + (size_t)t * kPcgBytes);
-    uint32_t *q = reinterpret_cast<uint32_t *>(p + 4);
-    p[0] = g.s_hi;
-    p[1] = g.s_lo;
-    p[2] = g.inc_hi;
-    p[3] = g.inc_lo;
-    q[0] = g.has32;
-    q[1] = g.u32;
-}
-
-__device__ __forceinline__ Deal load_pool(const KArena &A, int t) {
-    SPL_CHECK(t >= 0 && t < A.n, BC_TABLE);
-    Deal d;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) d.board[k] = A.pool[(size_t)(PL_BOARD + k) * A.n + t];
-    d.nob0 = A.pool[(size_t)PL_NOB0 * A.n + t];
-    d.nob1 = A.pool[(size_t)PL_NOB1 * A.n + t];
-    return d;
-}
-__device__ __forceinline__ void store_pool(const KArena &A, int t, const Deal &d) {
-    SPL_CHECK(t >= 0 && t < A.n, BC_TABLE);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) A.pool[(size_t)(PL_BOARD + k) * A.n + t] = d.board[k];
-    A.pool[(size_t)PL_NOB0 * A.n + t] = d.nob0;
-    A.pool[(size_t)PL_NOB1 * A.n + t] = d.nob1;
-}
-
-// Deal the next episode into slot record `slot` from the table's engine-seed stream
-// (envs/splendor_env.py:43-44: reset() continues self.np_random).  Returns SPL_F_* bits.
-// A table never reset with a seed has no stream: it deals engine seed 0 (documented in
-// splendor_amd.h) and its record stays unseeded.
-template <int P>
-__device__ __forceinline__ uint32_t deal_next(const KArena &A, int t, int slot, uint8_t *scr, Deal &d, uint32_t *mtx) {
-    Pcg64 g = load_pcg(A, t);
-    uint32_t seed = 0u;
-    if (g.valid()) {
-        seed = g.engine_seed();
-        store_pcg(A, t, g);
-    }
-    return deal_into(seed, P, slot_rec(A, t, slot), scr, d, mtx);
-}
-
-template <int P>
-__device__ __forceinline__ void load_tab(Tab<P> &T, const KArena &A, int t) {
-    SPL_CHECK(t >= 0 && t < A.n, BC_TABLE);
-#pragma unroll
-    for (int w = 0; w < SW_COUNT; ++w) T.sw[w] = A.planes[(size_t)w * A.n + t];
-#pragma unroll
-    for (int q = 0; q < P; ++q)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) T.pw[q][k] = A.planes[(size_t)pw_index(q, k) * A.n + t];
-}
-
-// The table state and its legal-mask cache entry: `legal` is legal_moves of T (as computed under the
-// context tagged `tag`), or anything with tag 0 when the storing kernel does not know it.  Every
-// kernel that stores state goes through here, so no stale mask survives a state change.
-template <int P>
-__device__ __forceinline__ void store_words(const Tab<P> &T, const KArena &A, int t) {  // state words only
-    SPL_CHECK(t >= 0 && t < A.n, BC_TABLE);
-#pragma unroll
-    for (int w = 0; w < SW_COUNT; ++w) A.planes[(size_t)w * A.n + t] = T.sw[w];
-#pragma unroll
-    for (int q = 0; q < P; ++q)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) A.planes[(size_t)pw_index(q, k) * A.n + t] = T.pw[q][k];
-}
-// `tag`: KTables::mtag (the shift drops its flag bit) or 0
-__device__ __forceinline__ void store_legal(const KArena &A, int t, uint64_t legal, uint32_t tag) {
-    static_assert(kLegalTagShift == 16 && kLegalTagMax == 0xFFFFu, "the tag is the low half of KTables::mtag");
-    A.legal[t] = (uint32_t)legal;
-    A.legal[A.n + t] = ((uint32_t)(legal >> 32) & kLegalHiBits) | (tag << kLegalTagShift);
-}
-template <int P>
-__device__ __forceinline__ void store_tab(const Tab<P> &T, const KArena &A, int t, uint64_t legal, uint32_t tag) {
-    store_words(T, A, t);
-    store_legal(A, t, legal, tag);
-}
-
-// the cached legal mask of table t's stored state, if it was computed under context tag `tag`
-struct LegalCache {
-    uint32_t lo, hi;
-    // tag 0 is "unknown" on both sides: an entry a crafted upload left, and a context without a tag of its
-    // own (card_table_tag ran out) never trusts an entry
-    // (`tag`: KTables::mtag, its flag bit above the tag ignored)
-    __device__ __forceinline__ bool known(uint32_t tag) const {
-        return (tag & kLegalTagMax) != 0u && (hi >> kLegalTagShift) == (tag & kLegalTagMax);
-    }
-    __device__ __forceinline__ uint64_t mask() const { return (uint64_t)lo | ((uint64_t)(hi & kLegalHiBits) << 32); }
-};
-__device__ __forceinline__ LegalCache load_legal(const KArena &A, int t) {
-    return LegalCache{A.legal[t], A.legal[A.n + t]};
-}
-
-__device__ __forceinline__ void load_tables_lds(Consts &L, const KTables &Tb) {
-    for (int i = lane_id(); i < 90; i += 64) L.cards[i] = Tb.cards[i];
-    if (lane_id() < 10) L.nobles[lane_id()] = Tb.nobles[lane_id()];
-}
-// The same tables by LDS-DMA from ONE wave (global_load_lds, 16 B per lane: 90 card records, then the
-// 80-B noble array as five 16-B pieces): no registers and no LDS write instructions, and the issuing
-// wave's own vmcnt covers their landing — a later s_waitcnt vmcnt(0) of that wave makes them readable
-// to it, and a barrier after that to the workgroup.
-typedef __attribute__((address_space(3))) void lds_void_t;
-__device__ __forceinline__ void dma_tables_lds(Consts &L, const KTables &Tb) {
-    const int lane = lane_id();
-    __builtin_amdgcn_global_load_lds(reinterpret_cast<const void *>(Tb.cards + lane), (lds_void_t *)&L.cards[0], 16, 0, 0);
-    if (lane < 26)
-        __builtin_amdgcn_global_load_lds(reinterpret_cast<const void *>(Tb.cards + 64 + lane), (lds_void_t *)&L.cards[64],
-                                         16, 0, 0);
-    if (lane < 5)
-        __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint8_t *>(Tb.nobles) + 16 * lane,
-                                         (lds_void_t *)&L.nobles[0], 16, 0, 0);
-}
-
-template <int P>
-__device__ __forceinline__ uint64_t legal_of(const Tab<P> &T, const Consts &L) {
-    uint32_t w[4];
-    get_player(T, get_to_play(T.sw), w);
-    const Pl p = unpack_pl(w);
-    int bank[6];
-    get_bank(T.sw, bank);
-    return legal_mask(T.sw, p, bank, L);
-}
-
-// the fused policies (spl_scripted.h) for a table whose state is in registers
-template <int P>
-__device__ __forceinline__ int policy_action(int policy, uint64_t m, const Tab<P> &T, const Consts &L,
-                                             uint64_t seed, uint64_t table, uint64_t ply) {
-    if (policy == SPL_POLICY_GREEDY_V1) return greedy_v1(m);
-    if (policy == SPL_POLICY_BASIC_PRIORITY)  // board points: obs[32 + 13k + 2]
-        return basic_priority(m, [&](int k, bool) { return (int)bget(card_rec(L, board_get(T.sw, k)).x, 2); }, seed,
-                              table, ply);
-    return sample_uniform(m, seed, table, ply);
-}
 
 // ------------------------------------------------------------------------------------------
 // kernels
@@ -711,330 +81,13 @@ __global__ __launch_bounds__(64) void k_build_lut(uint4 *lut) {
     lut[e] = make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-// ---- one env step of one table, shared by step_ws and the rollouts ----------------------------
+}  // namespace spl
 
-// Loads a step needs beyond the table state, issued as early as the action is known: the deck
-// card the action pops and the token-return table entry it consults (predict_lut_key).
-struct StepPre {
-    uint32_t top;
-    int key;
-    uint4 e;
-};
+#include "spl_engine_step.h"
+#include "spl_engine_cols.h"
+#include "spl_engine_ws.h"
 
-template <int P>
-__device__ __forceinline__ StepPre step_prefetch(const Tab<P> &T, int action, bool valid, const KArena &A, int t,
-                                                 const KTables &Tb) {
-    StepPre pre{0xFFu, -1, make_uint4(0u, 0u, 0u, 0u)};
-    const bool live_tab = valid && !is_terminal(T.sw);
-    const int ptier = pop_tier(action);
-    if (live_tab && ptier >= 0) {
-        const int len = (int)bget(T.sw[SW_DECK], ptier);
-        const uint8_t *live = live_rec(A, t, T.sw[SW_MISC]);
-        SPL_CHECK(len <= tier_size(ptier), BC_DECK);
-        if (len > 0) pre.top = abl(ABL_DECK_GATHER) ? (uint32_t)(len + 3 * ptier) : live[tier_base(ptier) + len - 1];
-    }
-    if (live_tab && action >= 0 && action < SPL_NUM_ACTIONS) {
-        const int tp = get_to_play(T.sw);
-        uint32_t pw4[4];
-        get_player(T, tp, pw4);
-        int bank[6];
-        get_bank(T.sw, bank);
-        pre.key = predict_lut_key(unpack_pl(pw4), bank, action, get_turn(T.sw), tp);
-        SPL_CHECK(pre.key < kLutEntries, BC_LUT);
-        if (pre.key >= 0) pre.e = abl(ABL_LUT_GATHER) ? make_uint4(0x12345678u, 0x9abcdef0u, 0x0fedcba9u, (uint32_t)pre.key) : Tb.lut[pre.key];
-    }
-    return pre;
-}
-
-constexpr uint64_t kMaskDeferred = 1ull << 63;  // step_rules(defer_mask): legal mask still to evaluate
-
-struct StepOut {
-    uint32_t flags;
-    float reward;
-    bool term;
-    uint64_t mask;  // info["action_mask"] after the step (before any autoreset)
-};
-
-// envs/splendor_env.py:51-90 on the table in registers.  `known` (k_rollout after its first
-// step): `known_mask` is legal_moves of the table's current state, computed by the previous step,
-// so "any legal move?" and mask[action] need no re-evaluation.
-template <int P, class Stamp = NoStamp>
-__device__ __forceinline__ StepOut step_rules(Tab<P> &T, int action, const StepPre &pre, bool valid, const Consts &L,
-                                              const KTables &Tb, uint32_t *mtx, bool known = false,
-                                              uint64_t known_mask = 0ull, bool defer_mask = false,
-                                              Stamp stamp = Stamp()) {
-    StepOut o{0u, 0.0f, false, 0ull};
-    bool want_mask = false;
-    if (valid) {
-        if (is_terminal(T.sw)) {                                  // :53-54 RuntimeError
-            o.flags = SPL_F_AFTER_TERMINAL;
-        } else {
-            const bool in_range = action >= 0 && action < SPL_NUM_ACTIONS;
-            uint32_t pw4[4];
-            get_player(T, get_to_play(T.sw), pw4);
-            const Pl cur = unpack_pl(pw4);
-            int bank[6];
-            get_bank(T.sw, bank);
-            // :55 mask = legal_moves(state): only "any legal?" and mask[action] are needed here
-            bool anyl, ok;
-            if (known) {
-                anyl = known_mask != 0ull;
-                ok = in_range && ((known_mask >> (action & 63)) & 1ull);
-            } else {
-                anyl = abl(ABL_LEGAL_PRE) || any_legal(T.sw, cur, bank, L);
-                ok = abl(ABL_LEGAL_PRE) || (in_range && action_legal(T.sw, cur, bank, action, L));
-            }
-            if (!anyl) {                                          // :56-61 no legal move: draw
-                T.sw[SW_MISC] = (T.sw[SW_MISC] | ST_GAME_OVER) & 0x00FFFFFFu;
-                T.sw[SW_BANK1] &= 0xFF00FFFFu;                    // to_play = 0
-                o.term = true;
-                o.flags = SPL_F_DRAW;
-            } else if (!in_range) {                               // :62-63 ValueError, mask of the unchanged state
-                o.flags = SPL_F_OOB;
-                want_mask = true;
-            } else if (!ok) {                                     // :64-66 illegal, mask of the unchanged state
-                o.flags = SPL_F_ILLEGAL;
-                o.reward = -0.01f;
-                want_mask = true;
-            } else {
-                STAMP(2);
-                stamp(4);
-                if (!abl(ABL_APPLY)) apply_action(T, action, pre.top, L, Tb.lut, pre.key, pre.e, mtx, stamp);  // :68
-                STAMP(3);
-                stamp(5);
-                o.term = is_terminal(T.sw);                       // :70
-                if (o.term) {                                     // :71-80
-                    const int w = get_winner(T.sw);
-                    const bool tl = (T.sw[SW_MISC] & ST_TURN_LIMIT) != 0;
-                    o.reward = (w < 0 && tl) ? -0.1f : (w < 0 ? 0.0f : (w == P - 1 ? 1.0f : -1.0f));
-                    o.flags |= tl ? SPL_F_TURN_LIMIT : 0u;        // :82-83
-                } else {
-                    want_mask = true;                             // :81
-                }
-            }
-        }
-    }
-    stamp(6);
-    // one legal_moves evaluation per lane (a single call site keeps one copy in the code).
-    // defer_mask: left to the caller (kMaskDeferred marks the lanes that need it; k_step_ws
-    // evaluates it after handing the state to its output wave)
-    if (defer_mask) o.mask = want_mask ? kMaskDeferred : 0ull;
-    else if (want_mask) o.mask = abl(ABL_LEGAL_POST) ? (uint64_t)action : legal_of(T, L);
-    return o;
-}
-
-// player 0's final reward of a finished episode (envs/splendor_env.py:92-115)
-template <int P>
-__device__ __forceinline__ float final_reward_p0(const Tab<P> &T) {
-    const int w = get_winner(T.sw);
-    const bool tl = (T.sw[SW_MISC] & ST_TURN_LIMIT) != 0;
-    return w < 0 ? (tl ? -0.1f : 0.0f) : (w == 0 ? 1.0f : -1.0f);
-}
-
-// Reset to the next episode of the table's engine-seed stream (envs/splendor_env.py:43-44:
-// reset() continues self.np_random): the live record moves to the next pool record, whose
-// board / noble words `pool` holds.  With every pool record consumed since the last refill the
-// next one is dealt inline — correct, only slower.  When the pool record after it is dealt, its
-// words are gathered into `pool` for the next reset (the caller stores them to the pool
-// planes); returns true in that case.
-template <int P>
-__device__ __forceinline__ bool flip_to_pool(Tab<P> &T, const KArena &A, int t, Deal &pool, uint8_t *scr,
-                                             uint32_t *mtx, uint32_t &flags) {
-    constexpr int kPools = kSlotRecords - 1;
-    const uint32_t misc = T.sw[SW_MISC];
-    const int a = active_of(misc), pend = pend_of(misc);
-    const int nxt = (a + 1) % kSlotRecords;
-    if (pend >= kPools) flags |= deal_next<P>(A, t, nxt, scr, pool, mtx);
-    const int pend2 = pend >= kPools ? kPools : pend + 1;  // the old live record is free now
-    fresh_state(T, ring_bits(nxt, pend2), pool);
-    if (pend2 < kPools) pool = rec_deal(slot_rec(A, t, (nxt + 1) % kSlotRecords));
-    return pend2 < kPools;
-}
-
-// One pool refill of table t (spl_refill's unit of work; status `misc` has pend > 0): re-deal the
-// earliest consumed record in ring order (the next episode's deal comes first in the engine-seed
-// stream).  When that record is the next pool, its words go to `pool` (`pool_dirty`).  Returns
-// the new status word.
-template <int P>
-__device__ __forceinline__ uint32_t refill_table(const KArena &A, int t, uint32_t misc, uint8_t *scr, uint32_t *mtx,
-                                                 Deal &pool, bool &pool_dirty) {
-    const int pend = pend_of(misc);
-    const int slot = (active_of(misc) + kSlotRecords - pend) % kSlotRecords;
-    Deal d;
-    deal_next<P>(A, t, slot, scr, d, mtx);
-    if (pend == kSlotRecords - 1) {
-        pool = d;
-        pool_dirty = true;
-    }
-    return (misc & ~ST_PEND) | ((uint32_t)(pend - 1) << ST_PEND_SHIFT);
-}
-
-// same-step autoreset of a terminal table; `pool_dirty` is set when the pool planes changed
-template <int P>
-__device__ __forceinline__ void autoreset_table(Tab<P> &T, const KArena &A, int t, Deal &pool, uint8_t *scr,
-                                                uint32_t *mtx, StepOut &o, bool &pool_dirty) {
-    pool_dirty |= flip_to_pool<P>(T, A, t, pool, scr, mtx, o.flags);
-    o.flags |= SPL_F_RESET;
-    o.mask = kFreshDealMask;
-}
-
-// The step mask of a lane whose table was just re-dealt (o.flags carries SPL_F_RESET; autoreset_table and
-// dealer_step left kFreshDealMask): under a card table with a free card, legal_moves of the dealt state.
-// The branch on the table's flag is wave-uniform (a kernel argument); other contexts do no work here.
-template <int P>
-__device__ __forceinline__ void fresh_deal_mask(StepOut &o, const Tab<P> &T, const Consts &L, const KTables &Tb) {
-    if (has_free_card(Tb) && (o.flags & SPL_F_RESET)) o.mask = legal_of(T, L);
-}
-
-// Terminal rows staged in L.frows (bits of `fin`) -> final_obs rows of this wave.
-__device__ __forceinline__ void store_final_rows(const uint8_t *rows_lds, uint64_t fin, int32_t *final_obs, int t0) {
-    while (fin) {
-        const int r = __ffsll((unsigned long long)fin) - 1;
-        fin &= fin - 1;
-        int32_t *dst = final_obs + (size_t)(t0 + r) * kObsDim;
-        for (int e = lane_id(); e < kObsDim; e += 64) dst[e] = (int32_t)rows_lds[r * kObsDim + e];
-    }
-}
-
-// ---- column-parallel rows (round 4) --------------------------------------------------------
-// A terminal table's info["final_observation"] row encoded by the whole wave: lane l owns bytes
-// e = l + 64 i (i < 5) of the ONE row and stores them as int32, coalesced (five 256-byte dword
-// stores).  encode_row's lane-per-row form costs every lane a whole row even when one or two of the
-// wave's 64 tables ended (random 4-player games end every ~30 steps: most steps), which made the
-// 4-player output wave's encode 4.4 us against 2.6 us at 2 players.  Here a byte is one or two LDS
-// reads plus a few VALU ops, driven by a per-lane recipe built once per launch (col_recipe): which
-// state word holds it (absolute, or a word of the player to move / the next player), which byte of
-// that word, and whether it names a card / noble whose record byte is the value
-// (engine/encode.py:124-187; the same fields as build_row).
-enum : uint32_t {
-    CK_BYTE = 0,      // the byte itself
-    CK_NRES = 1,      // & 3 (n_reserved of PW3)
-    CK_BOARD = 2,     // board card id -> record byte f (0 when the slot is empty)
-    CK_OWN_RES = 3,   // own reserved card slot s (PW3 byte s + 1) -> record byte f, f == 13: present
-    CK_OPP_RES = 4,   // opponent's reserved slot s: as own, hidden (not revealed) -> zeros
-    CK_NOBLE = 5,     // visible noble slot s (SW_NOB0 byte s) -> noble record byte f
-    CK_MOVES = 6,     // move_count, the full value (no byte patch needed)
-    CK_TERMINAL = 7,  // game_over and to_play == 0
-    CK_NONE = 8       // past the row
-};
-// recipe: word (5 bits) | rel << 5 (0 absolute, 1 to_play's PW, 2 next player's PW) | byte << 7 |
-//         kind << 9 | f << 13 | s << 17
-__device__ __forceinline__ uint32_t col_recipe(int e) {
-    auto R = [](int w, int rel, int b, uint32_t kind, int f = 0, int s = 0) {
-        return (uint32_t)w | ((uint32_t)rel << 5) | ((uint32_t)b << 7) | (kind << 9) | ((uint32_t)f << 13) |
-               ((uint32_t)s << 17);
-    };
-    if (e >= kObsDim) return R(0, 0, 0, CK_NONE);
-    if (e < 4) return R(SW_BANK0, 0, e, CK_BYTE);                                   // bank :128
-    if (e < 6) return R(SW_BANK1, 0, e - 4, CK_BYTE);
-    if (e < 32) {                                                                    // players :131-142
-        const int rel = e < 19 ? 1 : 2, q = e - (e < 19 ? 6 : 19);
-        return q < 12 ? R(q >> 2, rel, q & 3, CK_BYTE) : R(3, rel, 0, CK_NRES);
-    }
-    if (e < 188) {                                                                   // board :144-147
-        const int k = (e - 32) / 13;
-        return R(SW_BOARD + k / 4, 0, k % 4, CK_BOARD, (e - 32) % 13);
-    }
-    if (e < 272) {                                                                   // reserved :151-168
-        const bool own = e < 230;
-        const int q = e - (own ? 188 : 230), s = q / 14;
-        return R(3, own ? 1 : 2, s + 1, own ? CK_OWN_RES : CK_OPP_RES, q % 14, s);
-    }
-    if (e < 290) {                                                                   // nobles[:3] :171-178
-        const int s = (e - 272) / 6;
-        return R(SW_NOB0, 0, s, CK_NOBLE, (e - 272) % 6, s);
-    }
-    if (e < 293) return R(SW_DECK, 0, e - 290, CK_BYTE);                            // deck sizes :180-181
-    if (e == 293) return R(SW_BANK1, 0, 3, CK_BYTE);                                // turn_count :183
-    if (e == 294) return R(SW_BANK1, 0, 2, CK_BYTE);                                // to_play :184
-    if (e == 295) return R(SW_MISC, 0, 0, CK_MOVES);                                // move_count :185
-    return R(SW_MISC, 0, 0, CK_TERMINAL);                                           // terminal :186
-}
-struct ColRecipes {
-    uint32_t r[5];
-};
-__device__ __forceinline__ ColRecipes col_recipes() {
-    ColRecipes c;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) c.r[i] = col_recipe(lane_id() + 64 * i);
-    return c;
-}
-
-// One table's observation row, column-parallel (wave-uniform call): word w of the table's state is
-// st[w * stride] in LDS (st and stride uniform); v[i] = column lane + 64 i of the row.
-template <int P>
-__device__ __forceinline__ void row_columns(const uint32_t *st, int stride, const Consts &L, const ColRecipes &C,
-                                            uint32_t (&v)[5]) {
-    const uint32_t bank1 = st[SW_BANK1 * stride], misc = st[SW_MISC * stride];
-    const int tp = (int)bget(bank1, 2), np = (tp + 1) % P;
-    const uint32_t deck = st[SW_DECK * stride], owners = (st[SW_NOB1 * stride] >> 8) & 0x7FFFu;
-    const uint8_t *cb = reinterpret_cast<const uint8_t *>(L.cards);
-    const uint8_t *nb = reinterpret_cast<const uint8_t *>(L.nobles);
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-        const uint32_t r = C.r[i];
-        const int w0 = (int)(r & 31u), rel = (int)((r >> 5) & 3u), b = (int)((r >> 7) & 3u);
-        const uint32_t kind = (r >> 9) & 15u;
-        const int f = (int)((r >> 13) & 15u), s = (int)((r >> 17) & 3u);
-        const int widx = rel == 0 ? w0 : pw_index(rel == 1 ? tp : np, w0);
-        const uint32_t w = st[widx * stride];
-        const uint32_t byte = bget(w, b);
-        // the record byte a card / noble kind reads (address clamped: read unconditionally)
-        const bool is_noble = kind == CK_NOBLE;
-        const uint32_t id = byte < (is_noble ? 10u : 90u) ? byte : 0u;
-        const uint32_t rec = is_noble ? (uint32_t)nb[id * 8 + (f < 6 ? f : 0)] : (uint32_t)cb[id * 16 + (f < 13 ? f : 0)];
-        const int nres = (int)(w & 3u), rev = (int)((w >> 2) & 7u);
-        const bool res_pr = s < nres && (kind == CK_OWN_RES || ((rev >> s) & 1));
-        const bool nob_pr = s < (int)bget(deck, 3) && ((owners >> (3 * s)) & 7u) == 0u && byte < 10u;
-        uint32_t out = byte;
-        out = kind == CK_NRES ? (w & 3u) : out;
-        out = kind == CK_BOARD ? (byte != 0xFFu ? rec : 0u) : out;
-        out = (kind == CK_OWN_RES || kind == CK_OPP_RES) ? (res_pr ? (f == 13 ? 1u : rec) : 0u) : out;
-        out = is_noble ? (nob_pr ? rec : 0u) : out;
-        out = kind == CK_MOVES ? (misc & 0xFFFFu) : out;
-        out = kind == CK_TERMINAL ? (((misc & ST_GAME_OVER) && tp == 0) ? 1u : 0u) : out;
-        v[i] = out;
-    }
-}
-template <int P>
-__device__ __forceinline__ void store_row_columns(const uint32_t *st, int stride, const Consts &L, const ColRecipes &C,
-                                                  int32_t *dst) {
-    uint32_t v[5];
-    row_columns<P>(st, stride, L, C, v);
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-        const int e = lane_id() + 64 * i;
-        if (e < kObsDim) dst[e] = (int32_t)v[i];
-    }
-}
-// spl_step_args_t.gate_*: the dual step's opponent moves only where the agent's move was applied
-// and left the game running (wrappers/dual_step_native.py:120-140, spl_dual_gate); elsewhere its
-// action becomes -1 (out of range: no move), written back so the caller sees the gated action.
-__device__ __forceinline__ int gated_action(const KStep &S, int t) {
-    int action = S.actions[t];
-    if (S.gate_terminated && (S.gate_terminated[t] != 0 || (S.gate_flags[t] & (SPL_F_ILLEGAL | SPL_F_OOB)) != 0)) {
-        action = -1;
-        const_cast<int32_t *>(S.actions)[t] = -1;
-    }
-    return action;
-}
-
-// spl_step's gymnasium info planes (illegal_action, draw, turn_limit as 0/1 bytes; truncated = 0) and the running
-// count of tables whose flags carry the reference's exceptions (out-of-range action, step after
-// termination): one atomic per wave that has any.  Wave-uniform call (the ballot).
-__device__ __forceinline__ void store_step_info(const KStep &S, int n, int t, bool valid, uint32_t f) {
-    if (S.info && valid) {
-        S.info[t] = (f & SPL_F_ILLEGAL) ? 1 : 0;
-        S.info[(size_t)n + t] = (f & SPL_F_DRAW) ? 1 : 0;
-        S.info[2 * (size_t)n + t] = (f & SPL_F_TURN_LIMIT) ? 1 : 0;
-        S.info[3 * (size_t)n + t] = 0;  // truncated
-    }
-    if (S.errors) {
-        const uint64_t bad = __ballot(valid && (f & (SPL_F_OOB | SPL_F_AFTER_TERMINAL)) != 0);
-        if (bad && lane_id() == __ffsll((unsigned long long)bad) - 1)
-            atomicAdd(S.errors, (unsigned long long)__popcll(bad));
-    }
-}
+namespace spl {
 
 // K consecutive env steps of every table with the device uniform-random policy: exactly K
 // spl_step launches with next_actions fed back as the next launch's actions (plies ply ..
@@ -1050,25 +103,6 @@ __device__ __forceinline__ void store_step_info(const KStep &S, int n, int t, bo
 // this wave's stores drain and the other waves keep HBM busy, where a separate k_refill launch
 // leaves HBM idle for its whole duration.  Trajectories do not depend on when a refill happens
 // (deals are taken from each table's engine-seed stream in episode order either way).
-// Fused pool refills of one rollout launch: `count` refills (one per refill period the launch
-// crosses), one per segment of K / count steps, each workgroup at its own offset within the segment
-// so that deals (VALU-bound) overlap other workgroups' stores.  Results do not depend on the slots.
-struct RefillSlots {
-    int seg, count, off;
-    __device__ __forceinline__ bool due(int k) const { return count > 0 && k < seg * count && k % seg == off; }
-};
-// `key` staggers the refill step per workgroup (per team in the multi-team kernels); results do not
-// depend on the schedule
-__device__ __forceinline__ RefillSlots refill_slots(int K, int count, uint32_t key = blockIdx.x) {
-    RefillSlots r{1, 0, 0};
-    if (count > 0) {
-        r.count = min(count, K);
-        r.seg = K / r.count;
-        r.off = (int)(((key * 0x9E3779B1u) >> 16) % (uint32_t)r.seg);
-    }
-    return r;
-}
-
 template <int P>
 __global__ __launch_bounds__(64) void k_rollout(KArena A, KTables Tb, KStep S, int K, int per_step, int refill) {
     __shared__ BlockLDS L;
@@ -1184,111 +218,6 @@ __global__ __launch_bounds__(64) void k_rollout(KArena A, KTables Tb, KStep S, i
     }
 }
 
-// ---- two-wave pipelined rollout -----------------------------------------------------------
-// k_rollout as a two-stage pipeline per 64 tables: workgroup = 2 waves, lane l of both = table
-// t0 + l.  The RULES wave runs the steps (SplendorEnv.step, autoreset, policy, small outputs,
-// fused refill) and hands each step's table state to the OUTPUT wave through LDS; the output
-// wave encodes the observation rows (and the terminal rows) and issues the step's block stores
-// while the rules wave already computes the next step.  With one wave per table block, a step
-// was the rules' dependency chains PLUS the store issue stalls of one instruction stream
-// (k_rollout: 12.4 us of the 15 us step with the observation stores compiled out); split over
-// two waves on two SIMDs, the step costs the longer of the two stages.
-//
-// Hand-off per step k (buffers k & 1, so the rules wave refills buffer b only after the output
-// wave has passed the next barrier, i.e. finished with it): the state words after the step
-// (post-autoreset), the info mask, and the terminal (pre-autoreset) states of the first kTerm
-// terminal lanes; the rules wave writes any further terminal rows itself (store_row_direct).
-// One s_barrier per step; LDS ordering by lgkmcnt(0) only — a workgroup fence would add
-// vmcnt(0) and make each wave wait for its own global stores.
-//
-// LDS per workgroup must stay <= 40 KB so that four workgroups (a 65 536-table grid) are resident
-// per CU.  At 3-4 players the larger state and terminal hand-off would overflow that, so the deal
-// scratch shrinks to the 100 bytes a deal uses (stride 25 dwords: odd, conflict-free byte lanes),
-// 3 players list at most 8 terminal states per step, and at 4 players the scratch lives inside the
-// rules wave's own state slot st[k & 1]: a deal (fused refill or inline autoreset deal) runs
-// before that slot is written for step k, and the output wave finished reading it (step k - 2)
-// before the hand-off barrier of step k - 1.
-// partner hand-off (rollout store kernels): another wave of the team (the dealer, or the rules wave of
-// the two-wave kernel) polls the pair's flag words so the output wave never waits on a global load
-// behind its own row stores (one in-order vmcnt)
-struct PtShared {
-    uint32_t pepoch;  // output wave -> poller: this launch's counter
-    uint32_t seq[2];  // output wave -> poller: tasks posted (pseq), partner tasks seen (cseq)
-    uint64_t in[3];   // poller -> output wave: partner progress; pseq << 32 | my next slot's flag;
-                      // cseq << 32 | the partner's next slot's flag
-    uint64_t qcons[2];  // quad kernel: in[2] by the parity of the rules step that polled it (the output
-                        // wave's step k reads the rules wave's step k - 1, published before the barrier
-                        // the output wave has passed: guide row 3's barrier between poll and loads)
-};
-
-template <int P>
-struct __align__(16) WsLDS : Consts {
-    static constexpr int kW = SW_COUNT + 4 * P;  // state words per table
-    static constexpr int kWaves = 2;             // rules + output
-    PtShared pt;
-    static constexpr int kTerm = P == 3 ? 7 : (P == 4 ? 15 : 16);  // terminal states listed per step (3p: 7, room for PtShared)
-    static constexpr int kScrStride = P == 2 ? kScratchStride : 100;
-    static constexpr bool kScrInSlot = P == 4;
-    static_assert(!kScrInSlot || kW * 64 * 4 >= 64 * kScrStride, "scratch must fit the state slot");
-    uint32_t st[2][kW][64];
-    uint32_t tst[2][kTerm][kW];
-    uint32_t small[2][64];  // the step's reward / terminated / flags / winner / episode event (pack_small)
-    uint64_t mask[2][64];
-    uint64_t fin[2];
-    uint32_t mbits[96];
-    uint8_t rows[64 * kObsDim];
-    uint8_t scr[kScrInSlot ? 16 : 64 * kScrStride];  // the rules wave's deal scratch (P < 4)
-    uint32_t mtx[kScrInSlot ? 624 : 0];               // deal continuation (LaneMT) at P = 4 (none below)
-    __device__ __forceinline__ uint8_t *scratch(int b, int lane) {
-        return kScrInSlot ? reinterpret_cast<uint8_t *>(&st[b][0][0]) + lane * kScrStride : &scr[lane * kScrStride];
-    }
-    // LDS for a deal's LaneMT continuation: this step's free state slot, unless it holds the scratch
-    __device__ __forceinline__ uint32_t *deal_mtx(int b) { return kScrInSlot ? mtx : &st[b][0][0]; }
-};
-static_assert(sizeof(WsLDS<2>) <= 40960 && sizeof(WsLDS<3>) <= 40960 && sizeof(WsLDS<4>) <= 40960,
-              "the two-wave rollout needs four workgroups per CU");
-
-template <int P>
-__device__ __forceinline__ uint32_t tab_word(const Tab<P> &T, int w) {
-    return w < SW_COUNT ? T.sw[w] : T.pw[(w - SW_COUNT) >> 2][(w - SW_COUNT) & 3];
-}
-template <int P>
-__device__ __forceinline__ void set_tab_word(Tab<P> &T, int w, uint32_t v) {
-    if (w < SW_COUNT) T.sw[w] = v;
-    else T.pw[(w - SW_COUNT) >> 2][(w - SW_COUNT) & 3] = v;
-}
-
-// The rules wave's per-step small outputs, packed for the hand-off: the OUTPUT wave issues every
-// global write of a step.  A store the rules wave issued would sit in its vmcnt queue ahead of
-// the next step's deck / token-table gathers (gfx9 counts loads and stores in one in-order
-// counter), so each step's first use of a gathered value would wait for a write acknowledgement
-// from behind the whole chip's observation stream: 12.8 -> 19.6 us per step once that stream
-// goes to HBM instead of the Infinity Cache (rollout store, 65 536 tables).
-// bits 0-7 flags, 8 terminated, 9 valid, 10-12 winner + 1, 13-15 reward code, 16-17 code of
-// player 0's final reward (envs/splendor_env.py:92-115), 18 episode ended (ep_return / ep_count).
-__device__ __forceinline__ uint32_t reward_code(float r) {
-    return r == 0.0f ? 0u : (r == -0.01f ? 1u : (r == -0.1f ? 2u : (r == 1.0f ? 3u : 4u)));
-}
-__device__ __forceinline__ float reward_of_code(uint32_t c) {
-    return c == 0u ? 0.0f : (c == 1u ? -0.01f : (c == 2u ? -0.1f : (c == 3u ? 1.0f : -1.0f)));
-}
-// player 0's final reward is one of 0, -1, -0.1, 1 (final_reward_p0)
-__device__ __forceinline__ uint32_t ep_code(float r) { return r == 0.0f ? 0u : (r == -1.0f ? 1u : (r == -0.1f ? 2u : 3u)); }
-__device__ __forceinline__ float ep_of_code(uint32_t c) {
-    return c == 0u ? 0.0f : (c == 1u ? -1.0f : (c == 2u ? -0.1f : 1.0f));
-}
-__device__ __forceinline__ uint32_t pack_small(bool valid, const StepOut &o, int winner, bool ep, float ep_add) {
-    return (o.flags & 0xFFu) | (o.term ? 1u << 8 : 0u) | (valid ? 1u << 9 : 0u) | ((uint32_t)(winner + 1) & 7u) << 10 |
-           reward_code(o.reward) << 13 | ep_code(ep_add) << 16 | (ep ? 1u << 18 : 0u);
-}
-
-__device__ __forceinline__ void ws_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's LDS writes have landed
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-}
-
 // SplendorEnv.step for every table with the rules / output split of the two-wave rollout, for ONE step:
 // 128-thread workgroups of 64 tables.  The RULES wave loads, steps and autoresets its tables and
 // hands the new state words (and the pre-reset words of tables that just ended) to the OUTPUT
@@ -1321,15 +250,6 @@ struct __align__(16) StepWsLDS : Consts {
     alignas(16) uint8_t rows[64 * kObsU8];
 };
 static_assert(sizeof(StepWsLDS<4>) <= 40960, "k_step_ws_* needs four workgroups per CU");
-
-// Bounded LDS waits (the dealer rollout's and the three-wave step's): a wait that runs out faults the
-// launch — the serial goes to the context's host-mapped fault word — instead of spinning forever.
-constexpr uint32_t kSpinLimit = 1u << 22;
-__device__ uint32_t g_spin_limit = kSpinLimit;
-__device__ __forceinline__ void signal_fault(const KStep &S) {
-    if (S.fault && lane_id() == 0)  // a vector store (system scope: write-through to the host-mapped word)
-        __hip_atomic_store(S.fault, S.fault_tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
 
 // hand-off 2 of the three-wave step (rules -> output wave) as an LDS counter: a bounded wait (a lost
 // hand-off faults the launch loudly, as the dealer rollout's waits do, instead of spinning)
@@ -1582,583 +502,11 @@ static const StepKernel kStepKernels[3 * 3] = {SPL_STEP_KERNELS(X)};
 #undef X
 #undef SPL_STEP_THREADS
 
-// Rollout-store delegation (rollout_ws<P, 64, true>, spl_ctx_set_rollout_delegation).  The
-// XCCs of an MI355X do not drain stores equally fast: with the rollout store's own write pattern
-// and nothing else running (tools/microbench_store_xcc.hip), workgroups on odd XCCs (odd blockIdx)
-// finish ~20 % after those on even XCCs, whichever addresses they write; in the kernel the slowest
-// XCC sets the launch time.  So workgroups pair up (2q on an even XCC, 2q+1 on the odd one next to
-// it), and on every `every`-th step the odd one stages its 64 tables' state words after the step
-// (4.3 KB at 2 players, against the 76 KB block it would store; it skips that step's encode) and
-// its even partner, done with its own steps first, encodes and stores the rows into the rollout
-// store (staging the encoded rows as bytes, 19 KB a block, measured ~1 % slower and moved 0.06 GB
-// more per launch).  Cross-XCC hand-off (the guide's valid form):
-// payload stored sc1 (write-through), the ready flag stored sc1 only after the payload has
-// completed, the consumer polls sc1 and loads the payload sc1 behind an agent-scope acquire.
-// Nothing waits unboundedly: a consumer that does not see a task within its time limit gives up,
-// and the producer stores every task whose `taken` flag it does not see itself (a row stored
-// twice is the same row).  Launch epochs live in the arena (each side counts its own launches),
-// so flags from earlier launches, graph replays included, never match.
-struct Deleg {
-    bool on, producer;
-    int every;
-    uint32_t epoch;
-    uint32_t *fl;      // the pair's flag lines
-    uint8_t *pay;      // the pair's payload slots
-    int pend, pend_k;  // producer: task staged at step pend_k, ready flag not yet set
-    uint32_t staged;   // producer: tasks staged (not stored here)
-    __device__ __forceinline__ uint32_t *ready_flag(int j) const { return fl + (DF_TASKS + 2 * j) * kFlagLine; }
-    __device__ __forceinline__ uint32_t *taken_flag(int j) const { return fl + (DF_TASKS + 2 * j + 1) * kFlagLine; }
-    __device__ __forceinline__ uint8_t *slot(int j) const { return pay + (size_t)j * kDelegPayload; }
-};
-__device__ __forceinline__ bool deleg_step(int k, int K, int every) {
-    return every > 0 && k % every == every / 2 - 1 && k + 2 < K && k / every < kDelegTasks;
-}
-// the shortest period that delegates at all; from it on the workgroups take their tables by the identity
-// map (delegation pairs blockIdx b and b + 1 on adjacent XCCs)
-__device__ __forceinline__ bool deleg_period(int every) { return every >= 4; }
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_of(const void *base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), (short)0, 0x7FFFFFF0, 0x00020000);
-}
-constexpr int kSc1 = 16;  // buffer-op aux bit: sc1 (write-through store / L1-bypassing load)
-// a flag poll: relaxed agent-scope atomic load = global_load_dword sc1 (MI355X_MICROARCH.md: L1
-// bypassed, L2-served), the poll form of the guide's hand-off rows
-__device__ __forceinline__ uint32_t flag_load(const uint32_t *f) {
-    return __hip_atomic_load(const_cast<uint32_t *>(f), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void flag_store(uint32_t *f, uint32_t v) {  // lane 0 only
-    if (lane_id() == 0) __builtin_amdgcn_raw_buffer_store_b32(v, rsrc_of(f), 0, 0, kSc1);
-}
-// a delegated step: the wave's 64 tables' state words after the step -> a delegation slot
-// ([word][lane], 256 contiguous bytes per word), sc1 (write-through) dword stores: relaxed agent-scope
-// atomic stores = global_store_dword sc1; slots are 128-byte aligned (kDelegPayload = 50 lines), so each
-// 128-byte line is written whole by one store instruction of this wave (the guide's row 3 store cell)
-template <int P>
-__device__ __forceinline__ void stage_state(const Tab<P> &T, uint8_t *slot) {
-    uint32_t *const base = reinterpret_cast<uint32_t *>(slot);
-#pragma unroll
-    for (int w = 0; w < num_words(P); ++w)
-        __hip_atomic_store(base + w * 64 + lane_id(), tab_word(T, w), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-static_assert(kDelegPayload % 128 == 0, "partner / delegation slots stay 128-byte aligned");
-// a delegation slot -> the staged tables' state (sc1 loads)
-template <int P>
-__device__ __forceinline__ void unstage_state(const uint8_t *slot, Tab<P> &T) {
-    const __amdgpu_buffer_rsrc_t r = rsrc_of(slot);
-    uint32_t v[num_words(P)];
-#pragma unroll
-    for (int w = 0; w < num_words(P); ++w)
-        v[w] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(r, (w * 64 + lane_id()) * 4, 0, kSc1);
-#pragma unroll
-    for (int w = 0; w < num_words(P); ++w) set_tab_word(T, w, v[w]);
-}
-// one staged task's rows (delegation or partner hand-off): the staged words -> rows in LDS -> the row
-// block (whole wave, 64 full rows)
-template <int P>
-__device__ __forceinline__ void store_staged_task(const uint8_t *slot, uint8_t *rows_lds, const Consts &C, int32_t *dst) {
-    Tab<P> T;
-    unstage_state(slot, T);
-    encode_row(T, rows_lds, C);
-    wave_lds_sync();
-    store_obs_block<64, true>(rows_lds, 64, dst);
-    wave_lds_sync();  // the block's LDS reads are done before the next task's rows land
-}
-// the output wave opens the launch: both workgroups of a full pair take part (the same test on both
-// sides), each counting its own launches
-__device__ __forceinline__ Deleg deleg_open(const KArena &A, int every) {
-    const size_t pair = blockIdx.x >> 1;
-    Deleg dl{false, false, every, 0u, A.dflags + pair * kDelegFlagWords, A.deleg + pair * kDelegTasks * kDelegPayload,
-             -1, -1, 0u};
-    if (deleg_period(every) && (int)(blockIdx.x | 1u) * 64 + 64 <= A.n) {
-        dl.on = true;
-        dl.producer = (blockIdx.x & 1u) != 0;
-        uint32_t *ep = dl.fl + (dl.producer ? DF_PROD_EPOCH : DF_CONS_EPOCH) * kFlagLine;
-        dl.epoch = __builtin_amdgcn_readfirstlane(flag_load(ep)) + 1u;
-        flag_store(ep, dl.epoch);
-    }
-    return dl;
-}
-// producer, at a delegated step k: the tables' words go to the step's slot; a step with a patched row
-// (`big_moves`; its rows are encoded in `rows_lds`) is stored here and the partner skips the task
-template <int P>
-__device__ __forceinline__ void deleg_stage(Deleg &dl, const Tab<P> &T, int k, bool big_moves, const uint8_t *rows_lds,
-                                            int32_t *dst) {
-    const int j = k / dl.every;
-    if (big_moves) {
-        store_obs_block<64, true>(rows_lds, 64, dst);
-        flag_store(dl.ready_flag(j), dl.epoch << 1 | 1u);
-    } else {
-        stage_state(T, dl.slot(j));
-        dl.staged |= 1u << j;
-        dl.pend = j;
-        dl.pend_k = k;
-    }
-}
-// producer, at the end of every step: the task staged two steps ago turns ready
-__device__ __forceinline__ void deleg_release(Deleg &dl, int k) {
-    if (dl.pend >= 0 && k == dl.pend_k + 2) {
-        // release (guide rule (2)): every sc1 store of the staged words has completed
-        // before the ready flag is stored; by now two steps of block stores sit behind
-        // them, so the wait also drains those
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-        flag_store(dl.ready_flag(dl.pend), dl.epoch << 1);
-        dl.pend = -1;
-    }
-}
-// consumer, after its own steps: the partner's staged blocks, each as soon as its ready flag shows
-template <int P>
-__device__ __forceinline__ void deleg_consume(const Deleg &dl, int K, uint8_t *rows_lds, const Consts &C, int32_t *obs,
-                                              int n) {
-    const int64_t pt0 = (int64_t)(blockIdx.x + 1) * 64;
-    const uint64_t limit = 200000;  // 2 ms of s_memrealtime (100 MHz) per task at most
-    for (int k = 0; k < K; ++k) {
-        if (!deleg_step(k, K, dl.every)) continue;
-        const int j = k / dl.every;
-        uint32_t f = 0;
-        const uint64_t t_start = __builtin_amdgcn_s_memrealtime();
-        for (;;) {
-            f = __builtin_amdgcn_readfirstlane(flag_load(dl.ready_flag(j)));
-            if ((f >> 1) == dl.epoch || __builtin_amdgcn_s_memrealtime() - t_start > limit) break;
-            __builtin_amdgcn_s_sleep(8);
-        }
-        if ((f >> 1) != dl.epoch) break;  // not seen in time: the producer stores the rest
-        if (f & 1u) continue;              // the producer stored it
-        flag_store(dl.taken_flag(j), dl.epoch);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        store_staged_task<P>(dl.slot(j), rows_lds, C, obs + ((size_t)k * (size_t)n + pt0) * kObsDim);
-    }
-}
-// producer, after its steps: every staged block whose taken flag is not visible is stored here
-template <int P>
-__device__ __forceinline__ void deleg_reclaim(const Deleg &dl, uint8_t *rows_lds, const Consts &C, int32_t *obs, int n,
-                                              int t0) {
-    for (int j = 0; j < kDelegTasks; ++j) {
-        if (!((dl.staged >> j) & 1u)) continue;
-        const int k = j * dl.every + dl.every / 2 - 1;
-        if (__builtin_amdgcn_readfirstlane(flag_load(dl.taken_flag(j))) == dl.epoch) continue;
-        store_staged_task<P>(dl.slot(j), rows_lds, C, obs + ((size_t)k * (size_t)n + t0) * kObsDim);
-    }
-}
+}  // namespace spl
 
-// ---- the dealer wave (rollout for grids of at most two workgroups per CU) ----------------------
-// A pool refill deal is a ~90 us serial integer chain per wave (MT19937 init, stream, Fisher-Yates).
-// Fused into the rules wave it stalls that wave's steps for its whole length: at 4 players a
-// 128-step launch needs ~8 of them per table, ~45 % of the rules wave's time on a half-full chip
-// (C4's 32 768 tables per GPU).  When the grid leaves room for a third wave per workgroup (two
-// workgroups of 64 tables per CU: 6 waves on 4 SIMDs), a DEALER wave deals instead, beside the
-// rules and output waves:
-//   * the rules wave owns the ring bookkeeping (status word: live record, pend = consumed records
-//     not yet requested) and posts a batch -- one record per table, the earliest consumed one, the
-//     next in the engine-seed stream -- whenever the dealer is idle and some table has pend > 0;
-//   * the dealer owns the engine-seed streams (PCG64 records) and the deal scratch; it deals the
-//     batch into the slot records (global) and the board / noble words into LDS, drains its stores
-//     (s_waitcnt vmcnt(0): the waves of a workgroup share one L1, so that is the workgroup-scope
-//     release), then counts the batch done;
-//   * a table that ends while its next record is in flight waits for the batch; one whose pool is
-//     spent (all three records consumed) posts a batch of its own and waits (the old inline deal).
-// Deals are taken from each stream in episode order either way, so results do not depend on when
-// a batch runs.  The three waves hand off through LDS counters (no s_barrier: the dealer cannot
-// join a per-step barrier while it runs a 90 us deal).
-struct DealerLDS {
-    static constexpr int kStride = 100;  // deal scratch bytes per lane (25 dwords: odd, conflict-free)
-    uint8_t scr[64 * kStride];
-    uint32_t mtx[624];        // the dealer's LaneMT continuation (one lane at a time)
-    uint32_t rdeal[5][64];    // board / noble words of the last batch's deals ([word][lane])
-    uint8_t rq[64];           // slot record to deal per table, 0xFF = none
-    uint32_t dreq, ddone;     // batches posted (rules wave) / dealt (dealer)
-    uint32_t rdone, odone;    // steps handed off by the rules wave / finished by the output wave
-    uint32_t stop;            // rules wave: no more batches
-    uint32_t rnd[2][64];      // the uniform policy's words of step k in slot k & 1, drawn by the output wave at step k - 2
-    uint32_t abort;           // a wait ran out (lds_wait_ge): every later wait returns at once
-};
-template <int P>
-struct __align__(16) WsDealLDS : WsLDS<P> {
-    static constexpr int kWaves = 3;  // rules + output + dealer
-    DealerLDS dl;
-};
-static_assert(sizeof(WsDealLDS<2>) <= 81920 && sizeof(WsDealLDS<3>) <= 81920 && sizeof(WsDealLDS<4>) <= 81920,
-              "the dealer rollout needs two workgroups per CU");
+#include "spl_engine_handoff.h"
 
-__device__ __forceinline__ uint32_t lds_poll(const uint32_t *p) {
-    const uint32_t v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // later LDS reads stay below the poll
-    return __builtin_amdgcn_readfirstlane(v);
-}
-// lane 0 publishes `v` after this wave's earlier LDS writes have landed
-__device__ __forceinline__ void lds_publish(uint32_t *p, uint32_t v) {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
-    if (lane_id() == 0) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-// Every wait is bounded (~2^22 polls, a fraction of a second; a legitimate wait is one deal, ~0.1 ms)
-// so that a lost hand-off never leaves waves spinning on the GPU.  A wait that runs out FAULTS the
-// workgroup, loudly, in every build (round 4; was a silent abort in the release library):
-//   * it sets the workgroup's abort word, so every later wait of the three waves returns false at once;
-//   * the rules wave stops stepping and leaves its tables' state unstored, the output wave stops storing
-//     and marks SPL_F_FAULT in the flags of every step it did not store, the dealer stops dealing —
-//     nothing reads or writes through an index taken from an unsettled hand-off;
-//   * the launch's serial goes into the context's host-mapped fault word (signal_fault), which
-//     spl_ctx_faults reads without synchronising (Engine / SplendorVectorEnv / bench.py raise on it).
-// spl_debug_set_spin_limit lowers the limit so a test can force the path (BC_SPIN still marks it in
-// the bounds-check build).
-// true once *p >= v; false when the wait ran out or another wave of the workgroup already faulted
-__device__ __forceinline__ bool lds_wait_ge(DealerLDS &D, const uint32_t *p, uint32_t v) {
-    const uint32_t limit = g_spin_limit;
-    for (uint32_t spins = 0; lds_poll(p) < v; ++spins) {
-        if (spins >= limit || lds_poll(&D.abort)) {
-            SPL_CHECK(false, BC_SPIN);
-            if (lane_id() == 0) __hip_atomic_store(&D.abort, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            return false;
-        }
-        __builtin_amdgcn_s_sleep(1);
-    }
-    return true;
-}
-__device__ __forceinline__ Deal deal_of_lds(const DealerLDS &D, int lane) {
-    return Deal{{D.rdeal[0][lane], D.rdeal[1][lane], D.rdeal[2][lane]}, D.rdeal[3][lane], D.rdeal[4][lane]};
-}
-
-// ---- partner hand-off (six-wave dealer rollout, per-step outputs; ctx partner_lead) -------------
-// Under the rollout store's write stream the XCCs do not keep the same pace: the C4 share's stamps put
-// the teams of one or two XCCs 7-16 % behind the rest (their observation-row stores issue slower;
-// without the row stores every XCC runs the same period, profiles/r04/wsstamps4_r04k.txt), and the
-// launch ends with the slowest team.  So a team that falls behind hands whole steps of observation
-// rows to the same team of the workgroup on the neighbouring XCC (blockIdx b ^ 1), whose OUTPUT wave
-// encodes and stores them between its own steps:
-//   * each side's output wave publishes its progress (steps done) every step and reads the partner's
-//     from its dealer's snapshot; when the partner is `lead` or more steps ahead and the next task
-//     slot is free (by a snapshot of that slot's flag), the step's state words go to the slot (sc1 stores, ~6 KB) instead of the encode
-//     and the 76 KB row block, and the slot's flag turns READY(launch, step) after a vmcnt(0) at the
-//     top of the next step (the guide's drained-sc1 hand-off: sc1 payload, vmcnt(0), sc1 flag);
-//   * at the top of each step the partner's output wave looks at the snapshot of the next slot's flag
-//     and takes at most one READY task: an agent-scope compare-and-swap READY -> TAKEN,
-//     the words loaded sc1, encoded and stored, the slot freed; after its own steps it keeps serving
-//     until the partner's DONE word shows (bounded by time: a partner that never finishes keeps its
-//     tasks);
-//   * at the end the producer posts DONE and claims back, by the same compare-and-swap, every task
-//     still READY, and stores those rows itself: each task's rows are stored once, by its flag's winner.
-// (The dealer wave as the consumer took too few tasks: a deal keeps it busy ~90 us at a time.  It does
-// poll the pair's flag words for its output wave between batches (pt_poll: LDS snapshots tagged with
-// the sequence numbers they are for), so that the output wave issues no global load it must wait for
-// behind its own row stores in the one in-order vmcnt; polled by the output wave itself, the hand-off
-// made every team slower than it won.)
-// Masks, small outputs and terminal rows stay with the producer; rows are encoded by the same code
-// from the same words, so results do not depend on who stores them.  Launch counters (one per side,
-// in the arena, zeroed with it; both sides count the same launches) tag every flag, so nothing from
-// an earlier launch or graph replay matches.
-struct PartnerLink {
-    bool on;
-    int side, lead;    // lead < 0: hand off whenever a slot is free (tests)
-    uint32_t e;        // this launch's counter value
-    uint32_t *fl;      // the pair's flag lines
-    uint8_t *pay;      // the pair's payload slots
-    int t0p;           // the partner team's first table
-    __device__ __forceinline__ uint32_t *line(int l) const { return fl + l * kFlagLine; }
-    __device__ __forceinline__ uint8_t *slot(int j) const { return pay + (size_t)j * kDelegPayload; }
-};
-constexpr uint32_t kPtReady = 1u, kPtTaken = 2u;
-constexpr uint64_t kPartnerWait = 500000;  // 5 ms of s_memrealtime (100 MHz): the consumer's wait for DONE
-__device__ __forceinline__ uint32_t pt_flag(uint32_t e, int k, uint32_t st) { return e << 16 | (uint32_t)k << 2 | st; }
-__device__ unsigned long long g_partner_stats[2];  // tasks stored by the partner / claimed back (diagnostics)
-
-// READY(launch, step) posted by an agent-scope atomic add (the guide's row 3: "each storing wave for
-// itself", after that wave's s_waitcnt vmcnt(0)).  `seen` is the producer's snapshot of the slot's flag
-// when it chose the slot: 0 or a value of an earlier launch, which nobody else writes in this launch (the
-// consumer writes only flags READY in this launch), so adding target - seen leaves exactly `target`.
-__device__ __forceinline__ void pt_post_ready(uint32_t *f, uint32_t target, uint32_t seen) {
-    if (lane_id() == 0) (void)__hip_atomic_fetch_add(f, target - seen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// The output wave's hand-off state: tasks posted (pseq) and the one staged but not yet READY (slot pend,
-// step pend_k, pend_seen the slot's flag as the producer saw it, for pt_post_ready), partner tasks seen
-// (cseq).  The flags and the partner's progress come from the poller's LDS snapshots.
-struct PtOut {
-    uint32_t pseq, cseq;
-    int pend, pend_k;
-    uint32_t pend_seen;
-};
-// the task staged last (if any): its words have completed, then READY
-__device__ __forceinline__ void pt_ready_staged(const PartnerLink &pl, PtOut &po) {
-    if (po.pend < 0) return;
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-    pt_post_ready(pl.line(pt_ready_line(po.pend)), pt_flag(pl.e, po.pend_k, kPtReady), po.pend_seen);
-    po.pend = -1;
-}
-// lane 0 moves a task flag READY -> TAKEN (agent scope: performed past the XCC's L2); wave-uniform
-__device__ __forceinline__ bool pt_claim(uint32_t *f, uint32_t ready) {
-    uint32_t seen = 0u;
-    if (lane_id() == 0) {
-        seen = ready;
-        __hip_atomic_compare_exchange_strong(f, &seen, (ready & ~3u) | kPtTaken, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                             __HIP_MEMORY_SCOPE_AGENT);
-    }
-    return (uint32_t)__builtin_amdgcn_readfirstlane(seen) == ready;
-}
-// consumer (the partner team's output wave): `v` = the flag of the partner's slot cseq; if it is READY,
-// claim it and store the task's rows (staged through `rows`); true if the slot held a task.  Which
-// form makes the staged words visible (MI355X_MICROARCH.md, "Valid forms" / the hand-off table):
-//   acquire = false: the quad kernel in its steps — the flag was polled by the rules wave (global_load_dword
-//     sc1) before an s_barrier this wave has passed since (row 3: agent-atomic flag, barrier between the
-//     poll and every load, sc1 global stores / buffer_load_dword sc1 loads, one workgroup per CU);
-//   acquire = true: everywhere else (the six-wave dealer, whose poller is not separated from this wave by
-//     a barrier, and every drain after the steps) — the consumer's "always" form: one poll, the claim,
-//     ONE agent acquire, then the loads (this wave's own loads need no further wait).
-template <int P>
-__device__ __forceinline__ bool pt_serve_v(const PartnerLink &pl, uint32_t &cseq, uint32_t v, uint8_t *rows,
-                                           const Consts &C, int32_t *obs, int n, bool acquire) {
-    if ((v & 3u) != kPtReady || (v >> 16) != pl.e) return false;
-    const int j = (pl.side ^ 1) * kPartnerSlots + (int)(cseq % kPartnerSlots);
-    ++cseq;  // tasks fill the ring in order: the next one is in the next slot, whoever stores this one
-    uint32_t *f = pl.line(pt_ready_line(j));
-    if (!pt_claim(f, v)) return true;
-    if (acquire) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    const int k = (int)((v >> 2) & 0x3FFFu);
-    store_staged_task<P>(pl.slot(j), rows, C, obs + ((size_t)k * (size_t)n + (size_t)pl.t0p) * kObsDim);
-    // the slot's words were read (the encode used them) before it is free again; no vmcnt wait: the
-    // rows' stores need not have completed
-    __asm__ volatile("" ::: "memory");
-    flag_store(f, 0u);
-    if (lane_id() == 0) atomicAdd(&g_partner_stats[0], 1ull);
-    return true;
-}
-__device__ __forceinline__ uint32_t pt_next_flag(const PartnerLink &pl, uint32_t cseq) {
-    return flag_load(pl.line(pt_ready_line((pl.side ^ 1) * kPartnerSlots + (int)(cseq % kPartnerSlots))));
-}
-// consumer, after its own steps: serve until the partner's DONE word shows (or kPartnerWait passes)
-template <int P>
-__device__ __forceinline__ void pt_drain(const PartnerLink &pl, uint32_t &cseq, uint8_t *rows, const Consts &C,
-                                         int32_t *obs, int n) {
-    const uint64_t t_start = __builtin_amdgcn_s_memrealtime();
-    for (;;) {
-        if (pt_serve_v<P>(pl, cseq, (uint32_t)__builtin_amdgcn_readfirstlane(pt_next_flag(pl, cseq)), rows, C, obs, n,
-                          true))
-            continue;
-        const uint32_t dn = (uint32_t)__builtin_amdgcn_readfirstlane(flag_load(pl.line(pt_done_line(pl.side ^ 1))));
-        if (dn == pl.e) {  // its READY flags were stored before DONE: what is left of them, then out
-            while (pt_serve_v<P>(pl, cseq, (uint32_t)__builtin_amdgcn_readfirstlane(pt_next_flag(pl, cseq)), rows, C,
-                                 obs, n, true)) {
-            }
-            return;
-        }
-        if (__builtin_amdgcn_s_memrealtime() - t_start > kPartnerWait) return;
-        __builtin_amdgcn_s_sleep(8);
-    }
-}
-// producer, at the end of its steps — and on a fault of its workgroup: the task staged
-// last (if any) turns READY, DONE is posted behind every READY flag (the partner's pt_drain stops
-// waiting), then every task the partner has not taken is claimed back by the same compare-and-swap
-// and its rows are stored here: each handed-off step's rows are stored once, whatever happened after
-template <int P>
-__device__ __forceinline__ void pt_close(const PartnerLink &pl, PtOut &po, uint8_t *rows, const Consts &C, int32_t *obs,
-                                         int n, int t0) {
-    pt_ready_staged(pl, po);
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // every READY flag has completed before DONE
-    flag_store(pl.line(pt_done_line(pl.side)), pl.e);
-    if (po.pseq == 0u) return;
-    uint32_t mine = 0u;  // lane j: slot j's flag (relaxed agent load: global_load sc1)
-    if (lane_id() < kPartnerSlots)
-        mine = __hip_atomic_load(pl.line(pt_ready_line(pl.side * kPartnerSlots + lane_id())), __ATOMIC_RELAXED,
-                                 __HIP_MEMORY_SCOPE_AGENT);
-    uint64_t rm = __ballot(lane_id() < kPartnerSlots && (mine & 3u) == kPtReady && (mine >> 16) == pl.e);
-    for (; rm; rm &= rm - 1) {
-        const int j = __ffsll((unsigned long long)rm) - 1;
-        const uint32_t vj = (uint32_t)__builtin_amdgcn_readlane((int)mine, j);
-        uint32_t *f = pl.line(pt_ready_line(pl.side * kPartnerSlots + j));
-        if (!pt_claim(f, vj)) continue;
-        const int kk = (int)((vj >> 2) & 0x3FFFu);
-        store_staged_task<P>(pl.slot(pl.side * kPartnerSlots + j), rows, C, obs + ((size_t)kk * (size_t)n + (size_t)t0) * kObsDim);
-        if (lane_id() == 0) atomicAdd(&g_partner_stats[1], 1ull);
-    }
-}
-
-// The poll of the pair's words for the output wave (a snapshot; tags say which slots), by the dealer
-// wave between batches or by the quad kernel's rules wave.
-// what a poller loads for its output wave: the partner's progress, this side's next slot's flag (slot
-// of task ps) and the partner's next slot's flag (slot of task cs); the loads are not waited for here
-struct PtPolled {
-    uint32_t a, b, c, ps, cs;
-};
-__device__ __forceinline__ PtPolled pt_load(PtShared &X, const PartnerLink &pl) {
-    PtPolled q;
-    q.ps = lds_poll(&X.seq[0]);
-    q.cs = lds_poll(&X.seq[1]);
-    q.a = flag_load(pl.line(pt_progress_line(pl.side ^ 1)));
-    q.b = flag_load(pl.line(pt_ready_line(pl.side * kPartnerSlots + (int)(q.ps % kPartnerSlots))));
-    q.c = flag_load(pl.line(pt_ready_line((pl.side ^ 1) * kPartnerSlots + (int)(q.cs % kPartnerSlots))));
-    return q;
-}
-// qpar >= 0: the consumer's entry by the polling step's parity (PtShared::qcons)
-__device__ __forceinline__ void pt_publish(PtShared &X, const PtPolled &q, int qpar = -1) {
-    const uint32_t a = (uint32_t)__builtin_amdgcn_readfirstlane(q.a), b = (uint32_t)__builtin_amdgcn_readfirstlane(q.b),
-                   c = (uint32_t)__builtin_amdgcn_readfirstlane(q.c);
-    if (lane_id() == 0) {
-        __hip_atomic_store(&X.in[0], (uint64_t)a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_store(&X.in[1], (uint64_t)q.ps << 32 | b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_store(qpar < 0 ? &X.in[2] : &X.qcons[qpar], (uint64_t)q.cs << 32 | c, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-}
-__device__ __forceinline__ void pt_poll(PtShared &X, const PartnerLink &pl) { pt_publish(X, pt_load(X, pl)); }
-// the quad kernel's poller, once per step of its rules wave (which issues no row stores): the words
-// loaded last step go to the output wave's snapshots, then new loads
-__device__ __forceinline__ void pt_poll_ahead(PtShared &X, const PartnerLink &pl, PtPolled &q, int k) {
-    if (k > 0) pt_publish(X, q, k & 1);
-    q = pt_load(X, pl);
-}
-__device__ __forceinline__ uint64_t lds_poll64(const uint64_t *p) {
-    const uint64_t v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)v) |
-           (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32;
-}
-// the output wave at the top of step k: the task staged last step turns READY, then at most one of the
-// partner's tasks, between this team's steps (the poller's snapshot of its next slot, if it is for the
-// task this wave expects).  The quad kernel reads the snapshot its rules wave published at step k - 1,
-// before the s_barrier of step k - 1 that this wave has passed (PtShared::qcons); the six-wave dealer
-// acquires instead.
-template <int P, bool kDealer>
-__device__ __forceinline__ void pt_step_top(const PartnerLink &pl, PtOut &po, PtShared &X, int k, uint8_t *rows,
-                                            const Consts &C, int32_t *obs, int n) {
-    pt_ready_staged(pl, po);
-    const uint64_t nx = kDealer ? lds_poll64(&X.in[2]) : lds_poll64(&X.qcons[(k + 1) & 1]);
-    if ((uint32_t)(nx >> 32) == po.cseq && pt_serve_v<P>(pl, po.cseq, (uint32_t)nx, rows, C, obs, n, kDealer) &&
-        lane_id() == 0)
-        __hip_atomic_store(&X.seq[1], po.cseq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-// the output wave with step k's state: hand the step's rows to the partner if it is `lead` steps ahead and
-// the next slot is free (or stale), by a snapshot taken for this very slot.  True: the words are staged
-// (READY follows at the top of the next step, or in pt_close) and this wave skips the encode and the rows.
-template <int P>
-__device__ __forceinline__ bool pt_hand_off(const PartnerLink &pl, PtOut &po, PtShared &X, const Tab<P> &T, int k) {
-    const uint32_t pp = (uint32_t)lds_poll64(&X.in[0]);
-    const uint64_t ms = lds_poll64(&X.in[1]);
-    const uint32_t sf = (uint32_t)ms;
-    const bool ahead = pl.lead < 0 || ((pp >> 16) == pl.e && (int)(pp & 0xFFFFu) >= k + pl.lead);
-    if (!(ahead && (uint32_t)(ms >> 32) == po.pseq && ((sf & 3u) == 0u || (sf >> 16) != pl.e))) return false;
-    const int j = pl.side * kPartnerSlots + (int)(po.pseq % kPartnerSlots);
-    stage_state(T, pl.slot(j));
-    po.pend = j;
-    po.pend_k = k;
-    po.pend_seen = (uint32_t)__builtin_amdgcn_readfirstlane(sf);
-    ++po.pseq;
-    if (lane_id() == 0) __hip_atomic_store(&X.seq[0], po.pseq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    return true;
-}
-
-// The dealer wave: batches until the rules wave stops and none is left.  An idle wait that runs out
-// ends the dealer quietly: a batch posted after that is never dealt, so the rules wave's wait for it
-// runs out and faults the launch (lds_wait_ge).  A faulted workgroup's dealer ends after its batch.
-template <int P>
-__device__ __forceinline__ void dealer_loop(DealerLDS &D, const KArena &A, int t0, const PartnerLink &pl, PtShared &X) {
-    const int lane = lane_id();
-    const uint32_t limit = g_spin_limit;
-    uint32_t done = 0;
-    for (;;) {
-        uint32_t req;
-        for (uint32_t spins = 0;; ++spins) {
-            if (lds_poll(&D.abort)) return;
-            req = lds_poll(&D.dreq);
-            if (req != done || lds_poll(&D.stop)) break;
-            if (pl.on) pt_poll(X, pl);
-            if (spins >= limit) {
-                SPL_CHECK(false, BC_SPIN);
-                break;
-            }
-            __builtin_amdgcn_s_sleep(4);
-        }
-        if (req == done) break;  // stopped (or idle too long), nothing pending
-        const int slot = D.rq[lane];
-        const int t = t0 + lane;
-        if (slot != 0xFF) {
-            SPL_CHECK(t < A.n && slot < kSlotRecords, BC_TABLE);
-            Deal d;
-            deal_next<P>(A, t, slot, &D.scr[lane * DealerLDS::kStride], d, D.mtx);
-            D.rdeal[0][lane] = d.board[0];
-            D.rdeal[1][lane] = d.board[1];
-            D.rdeal[2][lane] = d.board[2];
-            D.rdeal[3][lane] = d.nob0;
-            D.rdeal[4][lane] = d.nob1;
-        }
-        __builtin_amdgcn_s_waitcnt(0);  // vmcnt(0): the records and engine-seed streams are written
-        lds_publish(&D.ddone, ++done);
-    }
-}
-
-// the rules wave posts a batch: lanes with `want` request slot record `slot` of their table
-__device__ __forceinline__ void dealer_post(DealerLDS &D, bool want, int slot, uint32_t &my_req) {
-    D.rq[lane_id()] = want ? (uint8_t)slot : (uint8_t)0xFF;
-    lds_publish(&D.dreq, ++my_req);
-}
-
-// The rules wave's side of the dealer after step_rules (wave-uniform call): settle a finished
-// batch, make sure every table that ended has its next record dealt (waiting for the batch in
-// flight, or posting one for a spent pool), run the same-step autoreset (flip_to_pool without its
-// inline deal), then post a new batch when the dealer is idle.  False: a wait for the dealer faulted
-// (lds_wait_ge) and T / pool were left as they were, not filled from an unsettled batch.
-template <int P>
-__device__ __forceinline__ bool dealer_step(DealerLDS &D, Tab<P> &T, const KArena &A, int t, bool valid, bool ends,
-                                            bool autoreset, Deal &pool, bool &pool_dirty, uint32_t &my_req,
-                                            uint32_t &infl, bool &pool_stale, StepOut &o) {
-    constexpr int kPools = kSlotRecords - 1;
-    const int lane = lane_id();
-    auto settle = [&]() {  // the last batch's records are dealt; its words fill a stale `pool`
-        infl = 0u;
-        if (pool_stale) {
-            pool = deal_of_lds(D, lane);
-            pool_stale = false;
-            pool_dirty = true;
-        }
-    };
-    bool idle = lds_poll(&D.ddone) == my_req;
-    if (idle) settle();
-    uint32_t misc = T.sw[SW_MISC];
-    int pend = pend_of(misc);
-    const int nxt = (active_of(misc) + 1) % kSlotRecords;
-    const bool spent = ends && pend >= kPools;  // all three pool records consumed: deal the next now
-    const bool blocked = ends && !spent && (((infl >> nxt) & 1u) != 0u || pool_stale);
-    if (__any(spent || blocked)) {
-        if (!idle) {
-            if (!lds_wait_ge(D, &D.ddone, my_req)) return false;
-            settle();
-            idle = true;
-        }
-        if (__any(spent)) {
-            dealer_post(D, spent, nxt, my_req);  // nxt is the earliest consumed record when pend == 3
-            if (spent) {
-                pend -= 1;
-                misc = (misc & ~ST_PEND) | ((uint32_t)pend << ST_PEND_SHIFT);
-                pool_stale = true;
-            }
-            if (!lds_wait_ge(D, &D.ddone, my_req)) return false;
-            settle();
-        }
-    }
-    if (ends) {  // flip_to_pool: the next record is dealt and `pool` holds its words
-        const int pend2 = pend + 1;  // the old live record is consumed
-        fresh_state(T, ring_bits(nxt, pend2), pool);
-        if (pend2 < kPools) {
-            const int nxt2 = (nxt + 1) % kSlotRecords;
-            if ((infl >> nxt2) & 1u) pool_stale = true;  // in flight: its words come with the batch
-            else pool = rec_deal(slot_rec(A, t, nxt2));
-        }
-        pool_dirty = true;
-        o.flags |= SPL_F_RESET;
-        o.mask = kFreshDealMask;
-        misc = T.sw[SW_MISC];
-        pend = pend2;
-    } else {
-        T.sw[SW_MISC] = misc;
-    }
-    const bool want = valid && autoreset && pend > 0;
-    if (idle && __any(want)) {  // refill: every table's earliest consumed record, next in its stream
-        const int slot = (active_of(misc) - pend + kSlotRecords) % kSlotRecords;
-        dealer_post(D, want, slot, my_req);
-        if (want) {
-            T.sw[SW_MISC] = (misc & ~ST_PEND) | ((uint32_t)(pend - 1) << ST_PEND_SHIFT);
-            infl = 1u << slot;
-            if (pend == kPools) pool_stale = true;  // the next record itself is being dealt
-        }
-    }
-    return true;
-}
+namespace spl {
 
 // TPW = tables per workgroup: 64, or 32 for grids too small to give every SIMD a wave (e.g. the
 // 32 768-table share of a 4-player 8-GPU run): twice the workgroups, lanes 32-63 idle.  The rules

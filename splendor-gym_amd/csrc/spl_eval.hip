@@ -2,7 +2,7 @@
 // scripts/eval_suite.py as a kernel over a mask and an observation, the legality check before a dual
 // step, the per-table tally after it and the reduction per opponent group.
 //
-// The step kernel fuses three of the policies (spl_engine.hip policy_action, fed from the table's state);
+// The step kernel fuses three of the policies (spl_engine_deal.h policy_action, fed from the table's state);
 // k_scripted runs the same functions of spl_scripted.h fed from the observation, and adds greedy_v2.
 // tests/test_gpu_eval_league.py pins the observation-fed kernel to the state-fed one action by action.
 #include "../../include/splendor_eval.h"

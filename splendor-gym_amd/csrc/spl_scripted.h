@@ -1,6 +1,6 @@
 // spl_scripted.h — the scripted policies over a 45-bit legal mask: the action classes, the uniform
 // draw and the k-th-legal-action sampler, and the two scripts/eval_suite.py cascades that the step
-// kernels fuse (spl_engine.hip policy_action, fed from the table's state) and that k_scripted runs
+// kernels fuse (spl_engine_deal.h policy_action, fed from the table's state) and that k_scripted runs
 // beside a network (spl_eval.hip, fed from the observation).  Their random choices are Philox draws
 // (sample_uniform over the preferred subset) where the reference calls np.random.choice.
 #pragma once

@@ -2,7 +2,7 @@
 
 The same names and values as the reference so ``from splendor_gym.engine.encode import
 OBSERVATION_DIM, TOTAL_ACTIONS`` (ppo_splendor.py:10) keeps working.  The encoding itself runs
-on the GPU (splendor-gym_amd/csrc/spl_engine.hip, encode_row).
+on the GPU (splendor-gym_amd/csrc/spl_engine_obs.h, encode_row).
 
 Observation (int32[297]):
     0-5     bank (white, blue, green, red, black, gold)

@@ -2,7 +2,7 @@
 // the deal's output stream, and the full Fisher-Yates deal with its LDS scratch, each on a
 // full grid (1024 waves, one per SIMD) and on the refill's typical grid (273 waves).
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 [-DMB_SCRATCH_STRIDE=112] tools/microbench_deal.hip -o ...
-#include "../splendor-gym_amd/csrc/spl_engine.hip"
+#include "../splendor-gym_amd/csrc/spl_engine_deal.h"
 
 using namespace spl;
 
@@ -31,9 +31,11 @@ __global__ __launch_bounds__(64) void k_init_outputs(uint32_t *out, uint32_t see
 
 __global__ __launch_bounds__(64) void k_deal(uint8_t *recs, uint32_t *out, uint32_t seed0) {
     __shared__ uint8_t scr_all[64 * kMbStride] __attribute__((aligned(16)));
+    __shared__ uint32_t mtx[624];  // the LaneMT continuation's state (spl_rng.h): never reached by these deals
     const uint32_t t = blockIdx.x * 64 + threadIdx.x;
     Deal d;
-    const uint32_t f = deal_into(seed0 + t * 2654435761u, 2, recs + (size_t)t * 128, &scr_all[threadIdx.x * kMbStride], d);
+    const uint32_t f = deal_into(seed0 + t * 2654435761u, 2, recs + (size_t)t * 128, &scr_all[threadIdx.x * kMbStride], d,
+                                 mtx);
     out[t] = d.board[0] ^ d.nob0 ^ f;
 }
 
