@@ -20,10 +20,11 @@
 //   spl_engine_cols.h      the column-parallel final rows                              (on args, base)
 //   spl_engine_ws.h        what the multi-wave kernels share, the bounded waits' parts (on args, base, rules, step)
 //   spl_engine_handoff.h   delegation, the dealer wave, the partner hand-off           (on all above but stamps, cols)
+//   spl_engine_succ.h      one-ply successors of every table, read-only               (on args, base, rules, obs, deal, step)
 // What stays here needs the translation unit, in the order it always had: k_build_lut (between the deal and the step
 // include), k_rollout, spl_step's kernels and kStepKernels (before the hand-off include: a kernel and a device
-// variable keep their order in the host object), the split-wave rollouts and kRolloutKernels, the utility kernels;
-// then the host side and the C ABI.
+// variable keep their order in the host object), the split-wave rollouts and kRolloutKernels, the utility kernels,
+// k_successors (last, behind its include: the kernels before it keep their order); then the host side and the C ABI.
 //
 // Reference semantics restated here (paths relative to the reference root):
 //   engine/rules.py:40-93 legal_moves, :101-122 _pay_for_card, :125-129 _refill_slot,
@@ -43,6 +44,7 @@
 #include <vector>
 
 #include "../../include/splendor_amd.h"
+#include "../../include/splendor_search.h"
 #include "spl_common.h"
 #include "spl_layout.h"
 #include "spl_rng.h"
@@ -1345,6 +1347,25 @@ __global__ __launch_bounds__(64) void k_upload(KArena A, int first, int count, c
 
 }  // namespace spl
 
+#include "spl_engine_succ.h"
+
+namespace spl {
+
+// spl_successors: one wave per (64-table block, action); grid (blocks, 45), the action in blockIdx.y (scalar)
+template <int P>
+__global__ __launch_bounds__(64) void k_successors(KArena A, KTables Tb, spl_succ_args_t S) {
+#ifdef SPL_SUCC_BLOCKLDS  // experiment builds: the rollout's staging block, the continuation in its terminal rows
+    __shared__ BlockLDS L;
+    uint32_t *const mtx = reinterpret_cast<uint32_t *>(L.frows);
+#else
+    __shared__ SuccLDS L;
+    uint32_t *const mtx = L.mtx;
+#endif
+    successors_wave<P>(L, mtx, A, Tb, S, (int)blockIdx.y);
+}
+
+}  // namespace spl
+
 // ==========================================================================================
 // host side: C-ABI
 // ==========================================================================================
@@ -2013,6 +2034,22 @@ int spl_table_upload(spl_ctx_t *ctx, spl_arena_t *arena, int32_t first, int32_t 
     if (int r = launch_check()) return r;
     HIP_TRY(hipStreamSynchronize(s));
     return SPL_OK;
+}
+
+int spl_search_abi_version(void) { return SPL_SEARCH_ABI; }
+
+int spl_successors(spl_ctx_t *ctx, spl_arena_t *arena, const spl_succ_args_t *a, void *stream) {
+    if (int r = check_arena(ctx, arena)) return r;
+    if (!a) return fail(SPL_E_ARG, "null successor arguments");
+    if (!a->obs && !a->obs_u8) return fail(SPL_E_ARG, "at least one of obs and obs_u8 must be given");
+    if (!a->flags || !a->reward) return fail(SPL_E_ARG, "null buffer: flags and reward are required");
+    if (spl_misaligned(a->obs, 16) || spl_misaligned(a->obs_u8, 16)) return fail(SPL_E_ARG, "obs and obs_u8 must be 16-byte aligned");
+    if (spl_misaligned(a->reward, 4) || spl_misaligned(a->mask_bits, 8))
+        return fail(SPL_E_ARG, "reward must be 4-byte aligned, mask_bits 8-byte aligned");
+    const KArena A = karena(arena);
+    DISPATCH_P(arena->players, hipLaunchKernelGGL(k_successors<PP>, dim3(blocks_for(arena->n), SPL_NUM_ACTIONS), dim3(64), 0,
+                                                  static_cast<hipStream_t>(stream), A, ktables(ctx), *a));
+    return launch_check();
 }
 
 }  // extern "C"

@@ -205,6 +205,21 @@ class EvalReduce(ctypes.Structure):
                                         "out")]
 
 
+SEARCH_ABI = 1  # SPL_SEARCH_ABI (include/splendor_search.h)
+SUCC_LEGAL, SUCC_TERMINATED, SUCC_TURN_LIMIT, SUCC_DREW = 0x01, 0x02, 0x04, 0x08  # SPL_SUCC_*
+
+
+class SuccArgs(ctypes.Structure):
+    """spl_succ_args_t (include/splendor_search.h)"""
+    _fields_ = [(k, c_void_p) for k in ("obs_u8", "obs", "flags", "reward", "mask_bits", "winner")]
+
+
+class PickArgs(ctypes.Structure):
+    """spl_pick_args_t (include/splendor_search.h)"""
+    _fields_ = [(k, c_void_p) for k in ("flags", "reward", "value", "action", "best_q")] + \
+               [("sign", ctypes.c_float), ("reserved", c_int32)]
+
+
 # spl_table_t (include/splendor_table.h) as a numpy structured dtype
 PLAYER_DTYPE = np.dtype([("tokens", "<i4", 6), ("bonuses", "<i4", 5), ("prestige", "<i4"),
                          ("n_reserved", "<i4"), ("reserved", "<i4", 3), ("revealed", "<i4", 3),
@@ -295,6 +310,10 @@ SIGNATURES = {
     "spl_eval_check": ([c_int32, ctypes.POINTER(EvalCheck), c_void_p], c_int32),
     "spl_eval_tally": ([c_int32, ctypes.POINTER(EvalTally), c_void_p], c_int32),
     "spl_eval_reduce": ([c_int32, c_int32, ctypes.POINTER(EvalReduce), c_void_p], c_int32),
+    # include/splendor_search.h
+    "spl_search_abi_version": ([], c_int32),
+    "spl_successors": ([c_void_p, ctypes.POINTER(ArenaDesc), ctypes.POINTER(SuccArgs), c_void_p], c_int32),
+    "spl_search_pick": ([c_int32, ctypes.POINTER(PickArgs), c_void_p], c_int32),
 }
 
 # what a library built from an earlier header may lack (SPLENDOR_AMD_LIB can name one): it still loads, and

@@ -14,6 +14,15 @@ from .engine.state import load_tables
 from .seeding import pcg64_states
 
 
+class Successors:
+    """What Engine.successors wrote: tensors shaped [45, n, ...]; a plane that was not asked for is None."""
+    __slots__ = ("obs", "obs_u8", "flags", "reward", "mask_bits", "winner")
+
+    def __init__(self, obs=None, obs_u8=None, flags=None, reward=None, mask_bits=None, winner=None):
+        self.obs, self.obs_u8, self.flags, self.reward = obs, obs_u8, flags, reward
+        self.mask_bits, self.winner = mask_bits, winner
+
+
 class Engine:
     """`num_tables` independent tables of `num_players` players on `device`.
 
@@ -387,6 +396,41 @@ class Engine:
         out = self.mask if out is None else out
         with self.torch.cuda.device(self.device):
             check(self.lib, self.lib.spl_legal(self.ctx, ctypes.byref(self.desc), ptr(out), self.stream()))
+        return out
+
+    def successors(self, obs=False, obs_u8=True, mask_bits=True, winner=False, out=None):
+        """Every table's 45 one-ply successors in one launch, read-only on the tables (spl_successors,
+        include/splendor_search.h): a Successors of action-major tensors, pair (t, a) at [a, t].  flags
+        (uint8, _native.SUCC_*) and reward (float32) always; obs int32 [45, n, 297], obs_u8 uint8
+        [45, n, 300] (at least one of the two), mask_bits int64 [45, n] (bits 0..44) and winner int8
+        [45, n] when asked.  Pairs without SUCC_LEGAL hold zero rows, flags 0, reward 0, mask_bits 0
+        and winner -1.  out: a Successors of an earlier call with the same planes, written again."""
+        torch = self.torch
+        if self.ctx is None:
+            raise RuntimeError("splendor engine: used after close()")
+        if not (obs or obs_u8):
+            raise ValueError("successors: at least one of obs and obs_u8")
+        n, dev = self.n, self.device
+        want = dict(obs=bool(obs), obs_u8=bool(obs_u8), mask_bits=bool(mask_bits), winner=bool(winner))
+        if out is None:
+            new = lambda shape, dt: torch.empty((NUM_ACTIONS, n) + shape, dtype=dt, device=dev)
+            out = Successors(obs=new((OBS_DIM,), torch.int32) if obs else None,
+                             obs_u8=new((OBS_U8,), torch.uint8) if obs_u8 else None,
+                             flags=new((), torch.uint8), reward=new((), torch.float32),
+                             mask_bits=new((), torch.int64) if mask_bits else None,
+                             winner=new((), torch.int8) if winner else None)
+        else:
+            for k, w in want.items():
+                if (getattr(out, k) is not None) != w:
+                    raise ValueError(f"successors: out.{k} does not match the planes asked for")
+            for k in ("obs", "obs_u8", "flags", "reward", "mask_bits", "winner"):
+                x = getattr(out, k)
+                if x is not None and not (x.device == dev and x.is_contiguous() and tuple(x.shape[:2]) == (NUM_ACTIONS, n)):
+                    raise ValueError(f"successors: out.{k} must be a contiguous [45, {n}, ...] tensor on {dev}")
+        a = _native.SuccArgs(obs_u8=ptr(out.obs_u8), obs=ptr(out.obs), flags=ptr(out.flags), reward=ptr(out.reward),
+                             mask_bits=ptr(out.mask_bits), winner=ptr(out.winner))
+        with torch.cuda.device(dev):
+            check(self.lib, self.lib.spl_successors(self.ctx, ctypes.byref(self.desc), ctypes.byref(a), self.stream()))
         return out
 
     def sample_uniform(self, mask=None, out=None, seed=0, ply=0):

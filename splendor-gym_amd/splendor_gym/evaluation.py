@@ -47,6 +47,8 @@ def eval_vs_opponent(agent_policy, opponent="greedy_v1", n_games=400, seed=0, de
     seeds = [int(rng.randint(1e9)) for _ in range(n_games)]
     env = DualStepVectorEnv(n_games, device=device, opponent=opponent, opponent_obs=False)
     try:
+        if hasattr(agent_policy, "bind"):  # a policy that reads the tables themselves (search.OnePlyValuePolicy)
+            agent_policy.bind(env)
         obs, info = env.reset(seeds=seeds)
         dev = env.device
         playing = torch.ones(n_games, dtype=torch.bool, device=dev)

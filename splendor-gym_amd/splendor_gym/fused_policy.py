@@ -143,14 +143,15 @@ class FusedActorCritic:
         return (action, logits) if want_logits else action
 
     def get_value(self, obs, out=None):
-        """ActorCritic.get_value (ppo_splendor.py:51): the critic's value, f32 [n, 1].  Needs
-        with_critic and an fp32 precision."""
+        """ActorCritic.get_value (ppo_splendor.py:51): the critic's value, f32 [n, 1], of int32 [n, 297]
+        observations or of compact uint8 [n, 300] rows.  Needs with_critic and an fp32 precision."""
         t = self.torch
         if not self.with_critic or self.precision not in _FP32_FORMS:
             raise ValueError("get_value needs an fp32 image with the critic")
-        if obs.dtype != t.int32 or obs.dim() != 2 or obs.shape[1] != OBS_DIM or not obs.is_contiguous() or \
-                obs.device != self.device:
-            raise ValueError("obs must be a contiguous int32 [n, 297] tensor on the policy's device")
+        u8 = obs.dtype == t.uint8  # compact rows (Engine.step obs_u8, Engine.successors)
+        if (obs.dtype != t.int32 and not u8) or obs.dim() != 2 or obs.shape[1] != (OBS_U8 if u8 else OBS_DIM) or \
+                not obs.is_contiguous() or obs.device != self.device:
+            raise ValueError("obs must be a contiguous int32 [n, 297] (or uint8 [n, 300]) tensor on the policy's device")
         value = out if out is not None else t.empty(obs.shape[0], 1, dtype=t.float32, device=self.device)
         self._run(obs, None, ACT_VALUE, None, value=value)
         return value
