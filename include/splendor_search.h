@@ -80,6 +80,52 @@ int spl_search_abi_version(void);
 int spl_successors(spl_ctx_t *ctx, spl_arena_t *arena, const spl_succ_args_t *args, void *stream);
 int spl_search_pick(int32_t n, const spl_pick_args_t *args, void *stream);
 
+/* ---- the ragged form: legal pairs only ------------------------------------------------------------------
+ * About one pair in six is legal, so the dense planes are mostly rows nobody reads.  spl_successors_pairs
+ * writes the legal pairs alone, compacted, and spl_search_pick_pairs picks over them.  SPL_SEARCH_ABI did not
+ * move: a library that has the two calls says so with SPL_SEARCH_PAIRS.
+ *
+ * The order of the pairs is a function of the arena alone.  With B = 64-table block t / 64:
+ *   pairs are sorted by (t / 64, a, t): block b's pairs are [base[b], base[b + 1]), inside it action a's pairs
+ *   come before action a + 1's, each in table order.  So with ballot_b(a) = the block's tables that allow a,
+ *     index(t, a) = base[t / 64] + sum over a' < a of popcount(ballot_b(a')) + rank of t in ballot_b(a),
+ *   computable from `legal` and `base` alone, and the rows of one (block, action) are contiguous.
+ * m = base[ceil(n / 64)] is the number of legal pairs.  If m > capacity nothing at an index >= capacity is
+ * written in any plane, and a (block, action) run that does not fit whole below capacity is not written at
+ * all; `legal` and `base` are complete all the same, so the host learns of the overflow from m, grows its
+ * buffers and calls again (the arena was only read).  No fault word is raised. */
+#define SPL_SEARCH_PAIRS 1
+
+typedef struct {
+    uint8_t *obs_u8;     /* [capacity][300], 16-byte aligned: compact rows                                 */
+    uint8_t *flags;      /* [capacity] SPL_SUCC_* (SPL_SUCC_LEGAL is set in every one)                     */
+    float *reward;       /* [capacity], 4-byte aligned                                                     */
+    int32_t *pair;       /* [capacity], 4-byte aligned: the dense index a * n + t of the pair              */
+    uint64_t *mask_bits; /* [capacity], 8-byte aligned, or NULL: as in spl_succ_args_t                     */
+    int8_t *winner;      /* [capacity], or NULL: as in spl_succ_args_t                                     */
+    uint64_t *legal;     /* [n], 8-byte aligned: legal_moves of table t's state, 0 for a table that is over */
+    int32_t *base;       /* [ceil(n / 64) + 1], 4-byte aligned: exclusive prefix of the blocks' pair counts */
+    int32_t capacity;    /* rows the buffers hold, >= 1                                                    */
+} spl_succ_pairs_args_t;
+
+/* spl_search_pick_pairs: spl_search_pick's semantics over the compacted planes.  A pair whose index is
+ * >= capacity takes no part: it is neither compared nor the first legal action. */
+typedef struct {
+    const uint64_t *legal; /* [n], 8-byte aligned                      */
+    const int32_t *base;   /* [ceil(n / 64) + 1], 4-byte aligned       */
+    const uint8_t *flags;  /* [m]                                      */
+    const float *reward;   /* [m], 4-byte aligned                      */
+    const float *value;    /* [m], 4-byte aligned                      */
+    int32_t *action;       /* [n] out, 4-byte aligned                  */
+    float *best_q;         /* [n] out, 4-byte aligned, or NULL         */
+    float sign;
+    int32_t capacity; /* pairs the planes hold, >= 1 */
+    int32_t reserved; /* 0 */
+} spl_pick_pairs_args_t;
+
+int spl_successors_pairs(spl_ctx_t *ctx, spl_arena_t *arena, const spl_succ_pairs_args_t *args, void *stream);
+int spl_search_pick_pairs(int32_t n, const spl_pick_pairs_args_t *args, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

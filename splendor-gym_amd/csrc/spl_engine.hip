@@ -21,10 +21,12 @@
 //   spl_engine_ws.h        what the multi-wave kernels share, the bounded waits' parts (on args, base, rules, step)
 //   spl_engine_handoff.h   delegation, the dealer wave, the partner hand-off           (on all above but stamps, cols)
 //   spl_engine_succ.h      one-ply successors of every table, read-only               (on args, base, rules, obs, deal, step)
+//   spl_engine_pairs.h     the successors of the legal pairs only, compacted           (on the succ layer and what it is on)
 // What stays here needs the translation unit, in the order it always had: k_build_lut (between the deal and the step
 // include), k_rollout, spl_step's kernels and kStepKernels (before the hand-off include: a kernel and a device
 // variable keep their order in the host object), the split-wave rollouts and kRolloutKernels, the utility kernels,
-// k_successors (last, behind its include: the kernels before it keep their order); then the host side and the C ABI.
+// k_successors (behind its include: the kernels before it keep their order) and the pairs kernels (last, behind
+// theirs, for the same reason); then the host side and the C ABI.
 //
 // Reference semantics restated here (paths relative to the reference root):
 //   engine/rules.py:40-93 legal_moves, :101-122 _pay_for_card, :125-129 _refill_slot,
@@ -1366,6 +1368,31 @@ __global__ __launch_bounds__(64) void k_successors(KArena A, KTables Tb, spl_suc
 
 }  // namespace spl
 
+#include "spl_engine_pairs.h"
+
+namespace spl {
+
+// spl_successors_pairs, three launches on one stream: the legal masks and block counts (one wave per 64 tables), their
+// prefix (one workgroup), and the rows: one wave per (64-table block, action), grid (blocks, 45) as k_successors
+template <int P>
+__global__ __launch_bounds__(64) void k_pairs_count(KArena A, KTables Tb, uint64_t *legal, int32_t *base) {
+    __shared__ Consts L;
+    pairs_count_wave<P>(L, A, Tb, legal, base);
+}
+
+__global__ __launch_bounds__(kPairsScanThreads) void k_pairs_scan(int32_t *base, int nb) {
+    __shared__ int32_t wsum[kPairsScanThreads / 64];
+    pairs_scan_block(base, nb, wsum);
+}
+
+template <int P>
+__global__ __launch_bounds__(64) void k_successors_pairs(KArena A, KTables Tb, spl_succ_pairs_args_t S) {
+    __shared__ SuccLDS L;
+    pairs_write_wave<P>(L, A, Tb, S, (int)blockIdx.y);
+}
+
+}  // namespace spl
+
 // ==========================================================================================
 // host side: C-ABI
 // ==========================================================================================
@@ -2049,6 +2076,29 @@ int spl_successors(spl_ctx_t *ctx, spl_arena_t *arena, const spl_succ_args_t *a,
     const KArena A = karena(arena);
     DISPATCH_P(arena->players, hipLaunchKernelGGL(k_successors<PP>, dim3(blocks_for(arena->n), SPL_NUM_ACTIONS), dim3(64), 0,
                                                   static_cast<hipStream_t>(stream), A, ktables(ctx), *a));
+    return launch_check();
+}
+
+int spl_successors_pairs(spl_ctx_t *ctx, spl_arena_t *arena, const spl_succ_pairs_args_t *a, void *stream) {
+    if (int r = check_arena(ctx, arena)) return r;
+    if (!a) return fail(SPL_E_ARG, "null successor arguments");
+    if (!a->obs_u8 || !a->flags || !a->reward || !a->pair || !a->legal || !a->base)
+        return fail(SPL_E_ARG, "null buffer: obs_u8, flags, reward, pair, legal and base are required");
+    if (spl_misaligned(a->obs_u8, 16)) return fail(SPL_E_ARG, "obs_u8 must be 16-byte aligned");
+    if (spl_misaligned(a->reward, 4) || spl_misaligned(a->pair, 4) || spl_misaligned(a->base, 4) ||
+        spl_misaligned(a->mask_bits, 8) || spl_misaligned(a->legal, 8))
+        return fail(SPL_E_ARG, "reward, pair and base must be 4-byte aligned, mask_bits and legal 8-byte aligned");
+    if (a->capacity < 1) return fail(SPL_E_ARG, "capacity must be positive");
+    if ((int64_t)SPL_NUM_ACTIONS * arena->n > INT32_MAX) return fail(SPL_E_ARG, "45 n pair indices do not fit int32: too many tables");
+    const KArena A = karena(arena);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const unsigned blocks = blocks_for(arena->n);
+    DISPATCH_P(arena->players, hipLaunchKernelGGL(k_pairs_count<PP>, dim3(blocks), dim3(64), 0, s, A, ktables(ctx), a->legal, a->base));
+    if (int r = launch_check()) return r;
+    hipLaunchKernelGGL(k_pairs_scan, dim3(1), dim3(kPairsScanThreads), 0, s, a->base, (int)blocks);
+    if (int r = launch_check()) return r;
+    DISPATCH_P(arena->players, hipLaunchKernelGGL(k_successors_pairs<PP>, dim3(blocks, SPL_NUM_ACTIONS), dim3(64), 0, s, A,
+                                                  ktables(ctx), *a));
     return launch_check();
 }
 

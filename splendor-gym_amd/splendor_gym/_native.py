@@ -220,6 +220,21 @@ class PickArgs(ctypes.Structure):
                [("sign", ctypes.c_float), ("reserved", c_int32)]
 
 
+SEARCH_PAIRS = 1  # SPL_SEARCH_PAIRS: the library has spl_successors_pairs / spl_search_pick_pairs
+
+
+class SuccPairsArgs(ctypes.Structure):
+    """spl_succ_pairs_args_t (include/splendor_search.h)"""
+    _fields_ = [(k, c_void_p) for k in ("obs_u8", "flags", "reward", "pair", "mask_bits", "winner", "legal", "base")] + \
+               [("capacity", c_int32)]
+
+
+class PickPairsArgs(ctypes.Structure):
+    """spl_pick_pairs_args_t (include/splendor_search.h)"""
+    _fields_ = [(k, c_void_p) for k in ("legal", "base", "flags", "reward", "value", "action", "best_q")] + \
+               [("sign", ctypes.c_float), ("capacity", c_int32), ("reserved", c_int32)]
+
+
 # spl_table_t (include/splendor_table.h) as a numpy structured dtype
 PLAYER_DTYPE = np.dtype([("tokens", "<i4", 6), ("bonuses", "<i4", 5), ("prestige", "<i4"),
                          ("n_reserved", "<i4"), ("reserved", "<i4", 3), ("revealed", "<i4", 3),
@@ -314,6 +329,8 @@ SIGNATURES = {
     "spl_search_abi_version": ([], c_int32),
     "spl_successors": ([c_void_p, ctypes.POINTER(ArenaDesc), ctypes.POINTER(SuccArgs), c_void_p], c_int32),
     "spl_search_pick": ([c_int32, ctypes.POINTER(PickArgs), c_void_p], c_int32),
+    "spl_successors_pairs": ([c_void_p, ctypes.POINTER(ArenaDesc), ctypes.POINTER(SuccPairsArgs), c_void_p], c_int32),
+    "spl_search_pick_pairs": ([c_int32, ctypes.POINTER(PickPairsArgs), c_void_p], c_int32),
 }
 
 # what a library built from an earlier header may lack (SPLENDOR_AMD_LIB can name one): it still loads, and

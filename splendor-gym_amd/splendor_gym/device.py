@@ -23,6 +23,23 @@ class Successors:
         self.mask_bits, self.winner = mask_bits, winner
 
 
+class SuccessorPairs:
+    """What Engine.successor_pairs wrote: the legal (table, action) pairs alone, `capacity` rows per plane of which
+    the first min(total(), capacity) are written, in the order include/splendor_search.h states (by 64-table block,
+    then action, then table).  pair holds the dense index a * n + t; legal [n] and base [ceil(n / 64) + 1] locate
+    a pair without it.  A plane that was not asked for is None."""
+    __slots__ = ("obs_u8", "flags", "reward", "pair", "mask_bits", "winner", "legal", "base", "capacity")
+
+    def __init__(self, obs_u8, flags, reward, pair, legal, base, capacity, mask_bits=None, winner=None):
+        self.obs_u8, self.flags, self.reward, self.pair = obs_u8, flags, reward, pair
+        self.mask_bits, self.winner, self.legal, self.base, self.capacity = mask_bits, winner, legal, base, int(capacity)
+
+    def total(self):
+        """m, the number of legal pairs (one 4-byte read from the device: it waits for the call).  More than
+        `capacity` means the planes are incomplete: call again with larger ones."""
+        return int(self.base[-1].item())
+
+
 class Engine:
     """`num_tables` independent tables of `num_players` players on `device`.
 
@@ -431,6 +448,47 @@ class Engine:
                              mask_bits=ptr(out.mask_bits), winner=ptr(out.winner))
         with torch.cuda.device(dev):
             check(self.lib, self.lib.spl_successors(self.ctx, ctypes.byref(self.desc), ctypes.byref(a), self.stream()))
+        return out
+
+    def successor_pairs(self, capacity=None, mask_bits=False, winner=False, out=None):
+        """The one-ply successors of the legal (table, action) pairs only, compacted, read-only on the tables
+        (spl_successors_pairs, include/splendor_search.h): a SuccessorPairs of `capacity` rows (default 12 n, above
+        the eight or so legal moves a table has on average).  The call is asynchronous; total() reads the number of
+        pairs m.  If m > capacity the rows at and beyond capacity, and a run cut by it, are not written: call again
+        with a larger capacity.  out: a SuccessorPairs of an earlier call with the same planes, written again
+        (its capacity holds)."""
+        torch = self.torch
+        if self.ctx is None:
+            raise RuntimeError("splendor engine: used after close()")
+        n, dev = self.n, self.device
+        nb = (n + 63) // 64
+        if out is None:
+            cap = 12 * n if capacity is None else int(capacity)
+            if cap < 1:
+                raise ValueError("successor_pairs: capacity must be positive")
+            new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+            out = SuccessorPairs(obs_u8=new((cap, OBS_U8), torch.uint8), flags=new((cap,), torch.uint8),
+                                 reward=new((cap,), torch.float32), pair=new((cap,), torch.int32),
+                                 mask_bits=new((cap,), torch.int64) if mask_bits else None,
+                                 winner=new((cap,), torch.int8) if winner else None,
+                                 legal=new((n,), torch.int64), base=new((nb + 1,), torch.int32), capacity=cap)
+        else:
+            cap = out.capacity
+            if capacity is not None and int(capacity) != cap:
+                raise ValueError("successor_pairs: capacity differs from out.capacity")
+            for k, w in (("mask_bits", bool(mask_bits)), ("winner", bool(winner))):
+                if (getattr(out, k) is not None) != w:
+                    raise ValueError(f"successor_pairs: out.{k} does not match the planes asked for")
+            for k, rows in (("obs_u8", cap), ("flags", cap), ("reward", cap), ("pair", cap), ("mask_bits", cap),
+                            ("winner", cap), ("legal", n), ("base", nb + 1)):
+                x = getattr(out, k)
+                if x is not None and not (x.device == dev and x.is_contiguous() and x.shape[0] >= rows):
+                    raise ValueError(f"successor_pairs: out.{k} must be a contiguous tensor of at least {rows} rows on {dev}")
+        a = _native.SuccPairsArgs(obs_u8=ptr(out.obs_u8), flags=ptr(out.flags), reward=ptr(out.reward), pair=ptr(out.pair),
+                                  mask_bits=ptr(out.mask_bits), winner=ptr(out.winner), legal=ptr(out.legal),
+                                  base=ptr(out.base), capacity=cap)
+        with torch.cuda.device(dev):
+            check(self.lib, self.lib.spl_successors_pairs(self.ctx, ctypes.byref(self.desc), ctypes.byref(a), self.stream()))
         return out
 
     def sample_uniform(self, mask=None, out=None, seed=0, ply=0):

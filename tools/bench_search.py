@@ -2,6 +2,8 @@
 
     python tools/bench_search.py [--tables 65536 1600] [--repeats 15] [--games 400] [--out profiles/search/bench_search.json]
     python tools/bench_search.py --ab plain=<lib> nt=<lib> ... [--rounds 5]      (row store policy / LDS shape A/B)
+    python tools/bench_search.py --part pairs [--tables ...] [--out profiles/search/bench_search_pairs.json]
+                                     (the legal pairs only: spl_successors_pairs and the compact decision against the dense ones)
 
 HIP events around each arm on one stream, the arms alternating, medians over `repeats`; two untimed calls of
 every arm first.
@@ -88,6 +90,66 @@ def pair_only(args):
     print(json.dumps({k: stats(v) for k, v in ms.items()}))
 
 
+def pairs_part(args):
+    """--part pairs: the ragged form against the dense one, same protocol: the pairs call against the dense call, and
+    the compact decision against the dense decision with its split (successors / read-back / critic / pick)."""
+    import torch
+    from splendor_gym.device import Engine
+    from splendor_gym.search import OnePlyValuePolicy, pick, pick_pairs
+
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    fused = golden_fused(torch, dev)
+    sizes = {}
+    for n in args.tables:
+        e = midgame(Engine, torch, n, dev)
+        s = e.successors(mask_bits=False)
+        p = e.successor_pairs()
+        m = p.total()
+        assert m <= p.capacity
+        rows = s.obs_u8.view(45 * n, 300)
+        value = torch.empty(45 * n, 1, dtype=torch.float32, device=dev)
+        value_m = torch.empty(p.capacity, 1, dtype=torch.float32, device=dev)
+        action = torch.empty(n, dtype=torch.int32, device=dev)
+        dense, compact = OnePlyValuePolicy(fused), OnePlyValuePolicy(fused, compact=True)
+        arms = {"successors": lambda: e.successors(mask_bits=False, out=s),
+                "successor_pairs": lambda: e.successor_pairs(out=p),
+                "critic_45n": lambda: fused.get_value(rows, out=value),
+                "critic_m": lambda: fused.get_value(p.obs_u8[:m], out=value_m[:m]),
+                "pick": lambda: pick(s.flags, s.reward, value, -1.0, out=action),
+                "pick_pairs": lambda: pick_pairs(p.legal, p.base, p.flags, p.reward, value_m, -1.0, capacity=m, out=action),
+                "read_back": lambda: p.total(),
+                "act_dense": lambda: dense.act(e),
+                "act_compact": lambda: compact.act(e)}
+        ms = timed(torch, arms, args.repeats)
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        same = bool(torch.equal(dense.act(e).clone(), compact.act(e)))
+        sizes[str(n)] = {
+            "us": {k: stats(v) for k, v in ms.items()},
+            "legal_pairs_m": m, "legal_share_of_pairs": round(m / (45 * n), 4),
+            "ratio_successors_over_pairs": round(med["successors"] / med["successor_pairs"], 2),
+            "ratio_act_dense_over_compact": round(med["act_dense"] / med["act_compact"], 2),
+            "act_compact_share": {k: round(med[k] / med["act_compact"], 3)
+                                  for k in ("successor_pairs", "read_back", "critic_m", "pick_pairs")},
+            "act_dense_share": {k: round(med[k] / med["act_dense"], 3) for k in ("successors", "critic_45n", "pick")},
+            "pairs_output_bytes": m * (300 + 1 + 4 + 4) + 8 * n, "dense_output_bytes": 45 * n * (300 + 1 + 4),
+            "equal_actions": same}
+        e.close()
+        del s, p, rows, value, value_m, dense, compact
+        torch.cuda.empty_cache()
+    line = json.dumps({"metric": "one-ply search over the legal pairs only against the dense form, 2 players, mid-game tables, "
+                                 "one MI355X",
+                       "timing": f"HIP events around each arm, arms alternating, medians of {args.repeats} (min and max are "
+                                 "the rounds' spread); two untimed calls of every arm first; read_back is the 4-byte "
+                                 "device read of m on an idle stream",
+                       "tables": sizes})
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
 def ab(args):
     libs = dict(x.split("=", 1) for x in args.ab)
     runs = {k: [] for k in libs}
@@ -126,6 +188,8 @@ def main():
         return ab(args)
     if args.part == "pair":
         return pair_only(args)
+    if args.part == "pairs":
+        return pairs_part(args)
 
     import torch
     from splendor_gym import _native
